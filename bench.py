@@ -3,8 +3,18 @@
 config 3: full fine-tune, adapters off, B=1024 per GPU, bf16 MFMA path), weak-scaled over
 N GPUs (one process per GPU, RCCL).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds the
+legs that take runs of their own after the timed steps: `parity_mode` (the bf16x3 mode timed on
+the same batch) and `cpu_baseline` (the CPU oracle).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (float32): the step's loss, features and logits, a fixed
+seeded sample of the updated parameters and of the (unclipped) gradients, and `grad_norm` =
+[total_norm, clip_coef], the factor AdamW applied to them.  Weights and batch are seeded, and
+with --dump-outputs the last timed step starts again from the seeded state (parameters, AdamW
+moments, step count; see main), so two runs or two builds with the same arguments can be
+compared output for output instead of at the end of a chaotic training trajectory.
 
 A step = forward of both towers + symmetric InfoNCE (all-gathered over ranks) + backward
 through everything + data-parallel gradient all-reduce + global-norm clip + AdamW, i.e.
@@ -14,9 +24,9 @@ once on the device; weights are random-init ViT-B/16 (no checkpoints offline).
 
 Rank 0 prints ONE JSON line.  `roofline` is measured live: the dominant kernel's launches
 inside the timed steps are bracketed by HIP events on their stream (clipmi_prof_*), and
-achieved = its algorithmic FLOPs per launch / average launch duration.  `cpu_baseline` is
-the CPU oracle (oracle/clip_ref.py, a restatement of the reference path) timed on this
-host's cores on a bounded sample.
+achieved = its algorithmic FLOPs per launch / average launch duration.  `cpu_baseline`
+(`--full` only) is the CPU oracle (oracle/clip_ref.py, a restatement of the reference path)
+timed on this host's cores on a bounded sample.
 """
 from __future__ import annotations
 
@@ -61,8 +71,13 @@ def parse():
                          "fp32: the parity mode (f32 operands end to end), priced against the f32 MFMA peak")
     ap.add_argument("--roofline-family", default=None, choices=list(FAMILIES) + list(FAMILIES_FP32),
                     help="family reported as `roofline` (default: the one with the most measured time)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: `parity_mode` "
+                         "(--parity-steps) and `cpu_baseline` (--cpu-sample); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-sample", type=int, default=32,
-                    help="pairs per CPU-baseline step (SURVEY 8d: B = 32; 0 = skip)")
+                    help="--full: pairs per CPU-baseline step (SURVEY 8d: B = 32; 0 = skip)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--comm", default="torch", choices=["torch", "clipmi"],
                     help="N > 1: the data-parallel exchanges through torch.distributed's RCCL (default) or RCCL issued "
@@ -70,7 +85,7 @@ def parse():
     ap.add_argument("--grad-bucket-dtype", default="fp32", choices=["fp32", "bf16"],
                     help="N > 1: dtype the gradient buckets are all-reduced in (bf16: half the bytes per ring)")
     ap.add_argument("--parity-steps", type=int, default=5,
-                    help="N=1, bf16 full fine-tune: also time this many steps of the bf16x3 mode (the mode that meets "
+                    help="--full, N=1, bf16 full fine-tune: also time this many steps of the bf16x3 mode (the mode that meets "
                          "north_star's 1e-3 logits) in the same run, reported under `parity_mode` (0 = skip)")
     ap.add_argument("--parity-warmup", type=int, default=2)
     ap.add_argument("--launch-check", action="store_true",
@@ -305,6 +320,39 @@ def family_roofline(name, launches, cfg, B, train, resid32=False, x3=False):
     return res
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per dumped array (4 MB of float32); larger ones are sampled
+
+
+def dump_outputs(path, out, arenas, grad_norm=None):
+    """--dump-outputs: what the last timed step handed its caller, as path/<name>.npy in float32: the
+    forward's outputs (loss, normalised features, logits) and, per parameter arena, the updated fp32
+    parameters (`params_arena<j>`) and the gradients of the backward as they lie in the arena
+    (`grads_arena<j>`).  Those gradients are NOT clipped: FusedAdamW.clip_grad_norm only computes
+    [total_norm, clip_coef] and the AdamW kernel multiplies by clip_coef in registers, so what the
+    optimizer consumed is grads * grad_norm[1]; `grad_norm` holds that pair.  An array of more than
+    DUMP_MAX_ELEMS elements is written as a sample of that many distinct (flattened) elements, at sorted
+    indices drawn from a seed that depends on the array's name alone, so every run samples the same
+    elements of an array whatever else is dumped beside it."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach() for k, v in out.items() if v is not None}
+    for j, a in enumerate(arenas):
+        arrays[f"params_arena{j}"] = a.data
+        arrays[f"grads_arena{j}"] = a.grad
+    if grad_norm is not None:
+        arrays["grad_norm"] = grad_norm
+    for name in sorted(arrays):
+        t = arrays[name].to(torch.float32)
+        if t.numel() > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(t.numel(), DUMP_MAX_ELEMS, replace=False, shuffle=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(t.cpu().numpy()))
+    log(f"dumped {len(arrays)} arrays to {path}: {' '.join(sorted(arrays))}")
+
+
 def parity_mode_run(args, cfg, dev, batch):
     """The bf16x3 mode (fp32 activations, every tower GEMM a bf16x3 split product: max |dlogit| 1.1e-4 against
     the fp32 reference at this config, profiles/r05_config3_full_size_parity.log; test bound 1e-3) timed on the
@@ -397,7 +445,25 @@ def main():
             opt.grads_all_reduce(group)
         opt.clip_grad_norm(1.0)
         opt.step(lr=5e-5 * linear_schedule_with_warmup(i, 0, total))
-        return loss
+        return out
+
+    # --dump-outputs: the dumped step must start from the same state in every run.  Training is chaotic at the
+    # last bit (float atomics in the bias and embedding gradients order-dependent, bf16 roundings flipping, AdamW
+    # turning near-zero gradients into +-lr), so after warmup + steps - 1 updates two runs of one build differ by
+    # far more than rounding (measured: logits by 0.03 between the first run on a cold device and later ones).
+    # So the last timed step, the one dumped, runs from the seeded initial state: parameters, AdamW moments and
+    # step count are put back just before it (three device copies / fills, ~1 ms of the timed region; only with
+    # --dump-outputs, a plain run is untouched).  It is the same step on the same batch, a real timed step.
+    init_state = [a.data.clone() for a in model.arenas()] if args.dump_outputs else None
+
+    def reset_to_init():
+        with torch.no_grad():
+            for a, d0 in zip(model.arenas(), init_state):
+                a.data.copy_(d0)  # bumps the version: the bf16 shadow is recast by the step's forward
+            for m_, v_ in opt.state:
+                m_.zero_()
+                v_.zero_()
+        opt.step_count = 0
 
     for i in range(args.warmup):
         t_w = time.perf_counter()
@@ -428,7 +494,10 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for i in range(args.warmup, total):
-        loss = step(i)
+        out = None  # release the previous step's outputs first: no step runs with another's logits alive
+        if init_state is not None and i == total - 1:
+            reset_to_init()
+        out = step(i)
         evs[i - args.warmup + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -441,6 +510,10 @@ def main():
         f"frees {ms_.get('num_device_free')} reserved peak {ms_.get('reserved_bytes.all.peak', 0) / 2**30:.1f} GiB "
         f"allocated peak {ms_.get('allocated_bytes.all.peak', 0) / 2**30:.1f} GiB")
     L.clipmi_prof_disarm()
+    loss = out["loss"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model.arenas(), opt.norm)
+    del out
     ms = (ctypes.c_float * cap)()
     fl = (ctypes.c_double * cap)()
     wh = (ctypes.c_int * cap)()
@@ -497,11 +570,12 @@ def main():
         "rooflines": {k: v for k, v in roofs.items() if k != main_fam},
         "cpu_baseline": None,
     }
-    if (world == 1 and args.parity_steps > 0 and args.precision == "bf16" and not adapters):
+    # --full: the legs that take runs of their own (a plain run ends with the headline's result line)
+    if (args.full and world == 1 and args.parity_steps > 0 and args.precision == "bf16" and not adapters):
         del model, opt, params
         torch.cuda.empty_cache()
         result["parity_mode"] = parity_mode_run(args, cfg, dev, batch)
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         result["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample, args.cpu_steps, adapters)
     if rank == 0:
         print(json.dumps(result), flush=True)

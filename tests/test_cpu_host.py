@@ -376,6 +376,47 @@ def test_bench_self_launches_n_ranks():
     assert sorted((d["rank"], d["world"]) for d in lines) == [(0, 2), (1, 2)]
 
 
+def test_bench_dump_outputs_is_float32_capped_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array the step returned plus each arena's parameters and gradients
+    lands as <name>.npy in float32; an array above the element cap is written as the same seeded sample on
+    every call (so two runs compare element for element); None outputs (streamed logits) are left out.
+    --full and --dump-outputs are off by default."""
+    import sys
+    import bench
+    from clipmi.arena import Arena
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None
+    # the largest dump bench.py can write: 5 forward outputs, parameters and gradients of 3 arenas (CLIP and
+    # the two adapters), grad_norm; each at most DUMP_MAX_ELEMS float32 -> within the 64 MB a dump may take
+    assert (5 + 2 * 3 + 1) * bench.DUMP_MAX_ELEMS * 4 <= 64e6
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 64)
+    ar = Arena([("w", (300,))], "cpu", dtype_shadow=False)
+    ar.data.copy_(torch.arange(ar.numel, dtype=torch.float32))
+    lt = torch.arange(20 * 20, dtype=torch.float64).view(20, 20)
+    out = {"loss": torch.tensor(1.5), "text_features": torch.ones(4, 8, dtype=torch.bfloat16),
+           "logits_per_text": lt, "logits_per_image": lt.t(), "missing": None}
+    norm = torch.tensor([4.0, 0.25])
+    got = []
+    for d, o in (("a", out), ("b", out), ("c", {"loss": out["loss"]})):
+        bench.dump_outputs(str(tmp_path / d), o, [ar], norm)
+        got.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert sorted(got[0]) == ["grad_norm", "grads_arena0", "logits_per_image", "logits_per_text", "loss",
+                              "params_arena0", "text_features"]
+    for k, v in got[0].items():
+        assert v.dtype == np.float32 and v.size <= 64
+        np.testing.assert_array_equal(v, got[1][k])
+    assert got[0]["loss"] == 1.5 and got[0]["text_features"].shape == (4, 8)
+    assert got[0]["grad_norm"].tolist() == [4.0, 0.25]
+    # a sample holds distinct elements of the array itself, in index order
+    p = got[0]["params_arena0"]
+    assert p.shape == (64,) and np.all(np.diff(p) > 0) and np.all(p == np.round(p)) and p.max() < ar.numel
+    li = got[0]["logits_per_image"]
+    assert len(set(li.tolist())) == 64 and set(li.tolist()) <= set(range(400))
+    # ... and which elements does not depend on what else is dumped (here: no logits beside it)
+    np.testing.assert_array_equal(got[2]["params_arena0"], p)
+
+
 @pytest.mark.parametrize("tag,cls,args", [("context", "ContextAdapter", (128, 2)), ("shared", "SharedAdapter", (96, 2)),
                                           ("textual", "TextualAdapter", (64, 32))])
 def test_peclip_modules_init_like_reference(golden, tag, cls, args):
