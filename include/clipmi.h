@@ -31,6 +31,7 @@ extern "C" {
 
 enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OCP e4m3 + E8M0 per 32 k */ };
 
+/* 2: clipmi_encoder_desc gained first_token (appended); clipmi_encoder_act_bytes */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -330,7 +331,24 @@ typedef struct clipmi_encoder_desc {
   int gemm_x3;
   void* x3_ws;
   int64_t x3_ws_bytes;
+  /* causal encoders only (clipmi_version() >= 2): compute token 0 of every sequence and nothing else.  Under a
+   * causal mask token 0 attends only to itself in every layer, so its output depends on row 0 of the input alone
+   * and, when only token 0 is pooled (model_m.py:102), every gradient at the other rows is exactly zero.
+   * Layout: the engine works on B rows, row b = token 0 of sequence b -- x_in, x_out, every act[l] buffer and dx
+   * are compact [B][.]; N stays the real sequence length and attention_mask stays [B, N] (mask[b * N] is read).
+   * Per layer: LN1, the V projection alone (rows [2D, 3D) of qkv_w, bias qkv_b + 2D; output [B][D] in act[l].qkv),
+   * O = V (a softmax over one key is 1; O = 0 where mask[b * N] == 0, as the attention kernels give a row with no
+   * valid key; act[l].qkv then holds O), out-projection + residual, LN2, fc1, fc2 on B rows.  act[l].o and
+   * act[l].lse are neither read nor written and may be NULL.  The backward mirrors it: dV = dO (same row select),
+   * the V weight / bias gradients into grads[l].qkv_w + 2D*D / grads[l].qkv_b + 2D; the q and k slots of both
+   * are NOT touched (gradients accumulate, and their exact value is zero).  Not with CLIPMI_FP8 or gemm_x3. */
+  int first_token;
 } clipmi_encoder_desc;
+/* Bytes of each clipmi_layer_act member for one layer in the descriptor's mode (dtype, resid_f32, gemm_x3,
+ * first_token; B, N, D, F, H), in member order: x_in, ln1, qkv, o, h, ln2, pre, act, mean1, rstd1, lse, mean2,
+ * rstd2.  0: the member is not used in this mode (may be NULL); pre is needed by a training forward only.
+ * Only the shape / mode fields of d are read. */
+int clipmi_encoder_act_bytes(const clipmi_encoder_desc* d, int64_t out[13]);
 int clipmi_encoder_fwd(void* stream, const clipmi_encoder_desc* d);
 int64_t clipmi_encoder_bwd_ws(const clipmi_encoder_desc* d);
 /* the split-image scratch of a gemm_x3 encoder (forward and backward; 0 when gemm_x3 is off) */

@@ -225,7 +225,13 @@ class CLIPWithAdapters(nn.Module):
         self._rt.train_tower = self._tower_training()
         ids = self._check_device(input_ids)
         mask = self._check_device(attention_mask) if attention_mask is not None else None
-        h = T.TextTowerFn.apply(ids, mask, _anchor(self.clip), self._rt)
+        if self.pooling == "first" and T.text_first_token(self._rt):
+            # the tower is causal and only token 0 is pooled (model_m.py:102): token 0 attends only to itself, so
+            # the other 76 rows never reach the features or any gradient -- the engine runs token 0's row alone
+            # ([B, 1, D]; the same values, 1/77 of the rows)
+            h = T.TextFirstTokenFn.apply(ids, mask, _anchor(self.clip), self._rt)
+        else:
+            h = T.TextTowerFn.apply(ids, mask, _anchor(self.clip), self._rt)
         idx = None
         if self.pooling == "eos":
             t = self.config.text_config

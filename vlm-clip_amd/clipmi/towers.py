@@ -59,7 +59,8 @@ class EncoderDesc(ctypes.Structure):
                 ("layers", ctypes.POINTER(LayerW)), ("grads", ctypes.POINTER(LayerG)),
                 ("act", ctypes.POINTER(LayerAct)), ("x_out", c_vp), ("workspace", c_vp),
                 ("workspace_bytes", c_i64), ("layers8", ctypes.POINTER(LayerW8)), ("q8", c_vp), ("s8", c_vp),
-                ("resid_f32", c_int), ("gemm_x3", c_int), ("x3_ws", c_vp), ("x3_ws_bytes", c_i64)]
+                ("resid_f32", c_int), ("gemm_x3", c_int), ("x3_ws", c_vp), ("x3_ws_bytes", c_i64),
+                ("first_token", c_int)]
 
 
 P = ctypes.POINTER
@@ -67,6 +68,7 @@ _lib.declare("clipmi_encoder_fwd", [c_vp, P(EncoderDesc)])
 _lib.declare("clipmi_encoder_bwd", [c_vp, P(EncoderDesc), c_vp])
 _lib.declare("clipmi_encoder_bwd_ws", [P(EncoderDesc)], c_i64)
 _lib.declare("clipmi_encoder_x3_ws", [P(EncoderDesc)], c_i64)
+_lib.declare("clipmi_encoder_act_bytes", [P(EncoderDesc), P(c_i64)])
 _lib.declare("clipmi_encoder_bwd_layers", [c_vp, P(EncoderDesc), c_vp, c_int, c_int])
 _lib.declare("clipmi_layernorm_fwd", [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                                       c_float, c_vp, c_vp, c_int])
@@ -237,24 +239,25 @@ class Encoder:
     def grads(self):
         return self._table(LayerG, self.arena.grad)
 
-    def alloc(self, B, N, dtype, device, train, resid32=False, x3=False):
-        """Activation storage: per-layer for training, one shared set for inference.  resid32: the
-        residual stream (x_in, h) in fp32 (the bf16 mode's fp32 residual stream).  x3 (the bf16x3 mode, fp32):
-        ln1 / ln2 / act as bf16 split images [R, 3K] and o followed by its image (include/clipmi.h gemm_x3)."""
+    def alloc(self, B, N, dtype, device, train, resid32=False, x3=False, first_token=False):
+        """Activation storage: per-layer for training, one shared set for inference.  The byte size of every
+        member comes from the engine (clipmi_encoder_act_bytes) for the descriptor's mode: resid32, the residual
+        stream (x_in, h) in fp32 (the bf16 mode's fp32 residual stream); x3 (the bf16x3 mode, fp32), ln1 / ln2 /
+        act as bf16 split images [R, 3K] and o followed by its image; first_token, B rows (token 0 of each
+        sequence) instead of B * N, no o and no lse (include/clipmi.h)."""
         t = self.t
-        R, D, F, H, L = B * N, t.hidden_size, t.intermediate_size, t.num_attention_heads, t.num_hidden_layers
-        es = 2 if dtype == torch.bfloat16 else 4
-        xs = 4 if resid32 else es
+        L = t.num_hidden_layers
+        d = EncoderDesc()
+        d.dtype, d.B, d.N, d.D, d.F, d.H, d.L = dcode(dtype), B, N, t.hidden_size, t.intermediate_size, \
+            t.num_attention_heads, L
+        d.causal = int(self.causal)
+        d.resid_f32 = int(resid32 and dtype == torch.bfloat16)
+        d.gemm_x3 = int(x3 and dtype == torch.float32)
+        d.first_token = int(first_token)
+        nb = (c_i64 * len(A_FIELDS))()
+        _lib.check(_lib.lib().clipmi_encoder_act_bytes(ctypes.byref(d), nb), "clipmi_encoder_act_bytes")
         al = lambda n: (n + 255) // 256 * 256  # noqa: E731
-        x3 = x3 and dtype == torch.float32
-        ln_b = R * 3 * D * 2 if x3 else R * D * es
-        o_b = al(R * D * 4) + R * 3 * D * 2 if x3 else R * D * es
-        act_b = R * 3 * F * 2 if x3 else R * F * es
-        parts = [("x_in", R * D * xs), ("ln1", ln_b), ("qkv", R * 3 * D * es), ("o", o_b),
-                 ("h", R * D * xs), ("ln2", ln_b), ("act", act_b),
-                 ("mean1", R * 4), ("rstd1", R * 4), ("lse", B * H * N * 4), ("mean2", R * 4), ("rstd2", R * 4)]
-        if train:
-            parts.append(("pre", R * F * es))
+        parts = [(name, int(n)) for name, n in zip(A_FIELDS, nb) if train or name != "pre"]
         per = sum(al(n) for _, n in parts)
         nsets = L if train else 1
         buf = torch.empty(per * nsets + 256, dtype=torch.uint8, device=device)
@@ -263,7 +266,7 @@ class Encoder:
         for i in range(L):
             off = base + per * (i if train else 0)
             for name, n in parts:
-                setattr(acts[i], name, off)
+                setattr(acts[i], name, off if n else None)  # 0 bytes: not used in this mode
                 off += al(n)
             if not train:
                 acts[i].pre = None
@@ -294,9 +297,11 @@ class Encoder:
         self._wcache["w8"] = (key, tab, keep)
         return tab
 
-    def desc(self, dtype, B, N, wbuf, acts, x_out, mask, grads=None, ws=None, fp8=False, resid32=False, x3=False):
+    def desc(self, dtype, B, N, wbuf, acts, x_out, mask, grads=None, ws=None, fp8=False, resid32=False, x3=False,
+             first_token=False):
         """x3: the bf16x3 mode (fp32 encoder, every GEMM a split-operand bf16 product); its split-image
-        scratch is allocated here and lives as long as the returned descriptor (d.x3_keep)."""
+        scratch is allocated here and lives as long as the returned descriptor (d.x3_keep).  first_token: the
+        engine's token-0 mode (compact [B] rows; causal towers, not with fp8 / x3: the engine rejects those)."""
         t = self.t
         d = EncoderDesc()
         d.dtype, d.B, d.N, d.D, d.F = dcode(dtype), B, N, t.hidden_size, t.intermediate_size
@@ -315,6 +320,7 @@ class Encoder:
         d.grads = grads
         d.act = acts
         d.x_out = x_out
+        d.first_token = int(first_token)
         if ws is not None:
             d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         if x3 and dtype == torch.float32:
@@ -574,6 +580,98 @@ class TextTowerFn(torch.autograd.Function):
         call("clipmi_text_embed_bwd", s, dc, P_(ctx.ids), P_(dx), R, D, V,
              arena.ptr("text_model.embeddings.token_embedding.weight", g), 1, P_(ews), ews.numel())
         call("clipmi_period_sum", s, dc, P_(dx), D, B, S, S, D,
+             arena.ptr("text_model.embeddings.position_embedding.weight", g), 1)
+        if hook is not None:  # token + position embeddings: the arena's first block
+            hook(arena, 0, arena.offsets["text_model.encoder.layers.0.layer_norm1.weight"][0])
+        ctx.buf = ctx.acts = ctx.xL = ctx.stats = None  # released with backward (see VisionTowerFn)
+        return None, None, None, None
+
+
+def text_first_token(rt):
+    """Whether first-token pooling may take TextFirstTokenFn: CLIPMI_TEXT_FIRST_TOKEN=0 forces the full tower
+    (A/B runs, tests); the fp8 towers keep the full path (the engine's first-token mode has no MXFP8 form)."""
+    return os.environ.get("CLIPMI_TEXT_FIRST_TOKEN", "1") != "0" and not (rt.fp8 and not rt.train_tower)
+
+
+class TextFirstTokenFn(torch.autograd.Function):
+    """TextTowerFn for first-token pooling (model_m.py:102, quirk Q1): the text tower is causal, so token 0
+    attends only to itself in every layer and the other tokens never reach the pooled feature or any gradient.
+    Embeds ids[:, 0] at position 0, runs the engine's first_token mode on B rows (include/clipmi.h) and the
+    final LayerNorm on those rows; returns [B, 1, D], the value of TextTowerFn(...)[:, :1].  The backward gives
+    the full tower's parameter gradients: those of token 0's path; the q / k projections' and the other
+    positions' are exactly zero and their slots are left as they are.  precision "bf16x3" runs these B rows in
+    exact fp32 (gemm_x3 = 0): at least as accurate as the split products, at a few milliseconds."""
+
+    @staticmethod
+    def forward(ctx, input_ids, attention_mask, anchor, runtime):
+        rt = runtime
+        arena, t, dtype = rt.arena, rt.cfg.text_config, rt.dtype
+        B, S = input_ids.shape
+        if S > t.max_position_embeddings:
+            raise ValueError(f"Sequence length must be less than max_position_embeddings (got `sequence length`: "
+                             f"{S} and max_position_embeddings: {t.max_position_embeddings}")
+        dev = input_ids.device
+        ids = input_ids.to(torch.int64)
+        mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous() if attention_mask is not None else None
+        D, V = t.hidden_size, t.vocab_size
+        train = rt.train_tower
+        s = K.stream()
+        dc = dcode(dtype)
+        wbuf = _wbuf(arena, dtype)
+        r32 = getattr(rt, "resid32", False)  # the fp32 residual stream (bf16 mode)
+        xdtype = torch.float32 if r32 else dtype
+        ids0 = ids[:, 0].contiguous()
+        bad = rt.bad_flag
+        # nn.Embedding's IndexError covers every position: an out-of-vocabulary id past token 0 still sets the flag
+        bad.logical_or_(((ids < 0) | (ids >= V)).any())
+        buf, acts = rt.tenc.alloc(B, S, dtype, dev, train, resid32=r32, first_token=True)
+        ebuf = arena.data if r32 else wbuf  # fp32 token / position embeddings into the fp32 stream
+        call("clipmi_text_embed", s, dcode(xdtype), P_(ids0), arena.ptr("text_model.embeddings.token_embedding.weight", ebuf),
+             arena.ptr("text_model.embeddings.position_embedding.weight", ebuf), acts[0].x_in, B, 1, D, V, P_(bad))
+        xL = torch.empty(B, D, dtype=xdtype, device=dev)
+        d = rt.tenc.desc(dtype, B, S, wbuf, acts, xL.data_ptr(), mask, resid32=r32, first_token=True)
+        _lib.check(_lib.lib().clipmi_encoder_fwd(s, ctypes.byref(d)), "clipmi_encoder_fwd")
+        del d
+        out = torch.empty(B, 1, D, dtype=dtype, device=dev)
+        stats = torch.empty(2, B, dtype=torch.float32, device=dev)
+        call("clipmi_layernorm_fwd2", s, dcode(xdtype), dc, P_(xL), D, P_(out), D,
+             arena.ptr("text_model.final_layer_norm.weight", wbuf), arena.ptr("text_model.final_layer_norm.bias", wbuf),
+             P_(stats[0]), P_(stats[1]), B, D, t.layer_norm_eps, None, None, 0)
+        if train:
+            ctx.rt, ctx.B, ctx.S, ctx.buf, ctx.acts = rt, B, S, buf, acts
+            ctx.ids0, ctx.mask, ctx.xL, ctx.stats, ctx.r32 = ids0, mask, xL, stats, r32
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        rt = ctx.rt
+        arena, t, dtype = rt.arena, rt.cfg.text_config, rt.dtype
+        B, S, D = ctx.B, ctx.S, t.hidden_size
+        dev = dout.device
+        s = K.stream()
+        dc = dcode(dtype)
+        arena.prepare_grads()
+        wbuf = _wbuf(arena, dtype)
+        g = arena.grad
+        dy = dout.to(dtype).contiguous()
+        dx = torch.empty(B, D, dtype=dtype, device=dev)
+        lws = _ws(_lib.lib().clipmi_layernorm_bwd_ws(B, D), dev)
+        call("clipmi_layernorm_bwd2", s, dcode(ctx.xL.dtype), dc, P_(dy), D, P_(ctx.xL), D, P_(ctx.stats[0]),
+             P_(ctx.stats[1]), arena.ptr("text_model.final_layer_norm.weight", wbuf), P_(dx), D, None, 0,
+             arena.ptr("text_model.final_layer_norm.weight", g), arena.ptr("text_model.final_layer_norm.bias", g), 1,
+             P_(lws), lws.numel(), B, D)
+        d = rt.tenc.desc(dtype, B, S, wbuf, ctx.acts, None, ctx.mask, grads=rt.tenc.grads(), resid32=ctx.r32,
+                         first_token=True)
+        ws = _ws(_lib.lib().clipmi_encoder_bwd_ws(ctypes.byref(d)), dev)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+        hook = _grad_hook(rt)
+        rt.tenc.backward(s, d, dx.data_ptr(), hook)
+        del d, ws
+        V = t.vocab_size
+        ews = _ws(_lib.lib().clipmi_text_embed_bwd_ws(B, V), dev)
+        call("clipmi_text_embed_bwd", s, dc, P_(ctx.ids0), P_(dx), B, D, V,
+             arena.ptr("text_model.embeddings.token_embedding.weight", g), 1, P_(ews), ews.numel())
+        call("clipmi_period_sum", s, dc, P_(dx), D, B, 1, 1, D,  # position 0's row alone
              arena.ptr("text_model.embeddings.position_embedding.weight", g), 1)
         if hook is not None:  # token + position embeddings: the arena's first block
             hook(arena, 0, arena.offsets["text_model.encoder.layers.0.layer_norm1.weight"][0])

@@ -15,6 +15,9 @@
 // column sums for biases, and LN backward with the residual gradient fused.
 // Activation buffers are caller-owned (per layer for training; one shared set for
 // inference), so the engine holds no state and allocates nothing.
+// first_token (causal encoders pooled at token 0, model_m.py:102): token 0 attends only to
+// itself, so the engine runs that row alone -- B compact rows, qkv reduced to the V projection,
+// o = V (no q, k, softmax or attention launch), the rest as above; see include/clipmi.h.
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
@@ -47,6 +50,8 @@ namespace {
 
 size_t esize(int dt) { return dt == CLIPMI_F32 ? 4 : 2; }
 int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+// rows the engine works on: every token, or token 0 of each sequence alone (first_token, clipmi.h)
+int64_t rows(const clipmi_encoder_desc* d) { return d->first_token ? (int64_t)d->B : (int64_t)d->B * d->N; }
 
 int gemm(void* s, int dt, int M, int N, int K, const void* A, int64_t lda, bool akm, const void* B, int64_t ldb,
          bool bkm, void* C, int64_t ldc, int c_dt, int flags, const void* bias = nullptr, const void* res = nullptr,
@@ -214,7 +219,7 @@ struct WsPlan {
 };
 
 WsPlan plan(const clipmi_encoder_desc* d) {
-  const int64_t R = (int64_t)d->B * d->N;
+  const int64_t R = rows(d);
   const size_t es = esize(d->dtype);
   WsPlan p;
   const int64_t big = std::max<int64_t>(3 * d->D, d->F);
@@ -287,6 +292,9 @@ int pending_hazard(const DeferredReduce& r, const void* dst, int64_t bytes, cons
 int validate(const clipmi_encoder_desc* d) {
   CLIPMI_REQUIRE(d && d->layers && d->act, "null descriptor");
   CLIPMI_REQUIRE(d->dtype == CLIPMI_BF16 || d->dtype == CLIPMI_F32 || d->dtype == CLIPMI_FP8, "dtype");
+  CLIPMI_REQUIRE(!d->first_token || d->causal, "first_token needs a causal encoder (token 0 must attend only to itself)");
+  CLIPMI_REQUIRE(!d->first_token || d->dtype != CLIPMI_FP8, "first_token: not with the fp8 encoder");
+  CLIPMI_REQUIRE(!d->first_token || !d->gemm_x3, "first_token: not with gemm_x3");
   CLIPMI_REQUIRE(d->dtype != CLIPMI_FP8 || (d->layers8 && d->q8 && d->s8), "fp8 encoder needs layers8 / q8 / s8");
   CLIPMI_REQUIRE(d->dtype != CLIPMI_FP8 || (d->D % 256 == 0 && d->F % 128 == 0),
                  "fp8 encoder: hidden size must be a multiple of 256 and the MLP width of 128");
@@ -296,6 +304,12 @@ int validate(const clipmi_encoder_desc* d) {
   CLIPMI_REQUIRE(!d->gemm_x3 || (d->x3_ws && d->x3_ws_bytes >= x3_bytes(d) && ((uintptr_t)d->x3_ws & 255) == 0),
                  "gemm_x3: x3_ws too small or not 256-byte aligned (clipmi_encoder_x3_ws)");
   return CLIPMI_OK;
+}
+
+// first_token: the rows of token 0 whose own key is padded get O = 0 / dV = 0 (in place; no launch without a mask)
+int select_rows(void* s, const clipmi_encoder_desc* d, void* x) {
+  if (!d->attention_mask) return CLIPMI_OK;
+  return mask_rows((hipStream_t)s, d->dtype, x, d->D, d->B, d->D, d->attention_mask, d->N);
 }
 
 int encoder_fwd_x3(void* s, const clipmi_encoder_desc* d) {
@@ -430,12 +444,35 @@ int encoder_bwd_x3(void* s, const clipmi_encoder_desc* d, void* dx, int layer_hi
 }  // namespace
 
 extern "C" int64_t clipmi_encoder_bwd_ws(const clipmi_encoder_desc* d) { return plan(d).total; }
+
+extern "C" int clipmi_encoder_act_bytes(const clipmi_encoder_desc* d, int64_t out[13]) {
+  CLIPMI_REQUIRE(d && out, "null argument");
+  CLIPMI_REQUIRE(d->dtype == CLIPMI_BF16 || d->dtype == CLIPMI_F32 || d->dtype == CLIPMI_FP8, "dtype");
+  CLIPMI_REQUIRE(d->B >= 0 && d->N >= 1 && d->D >= 1 && d->F >= 1 && d->H >= 1, "shape");
+  const int64_t R = rows(d), D = d->D, F = d->F;
+  const int64_t es = (int64_t)esize(d->dtype);                                // fp8: bf16 activations
+  const int64_t xs = (d->dtype == CLIPMI_BF16 && d->resid_f32) ? 4 : es;      // the residual stream (x_in, h)
+  const bool x3 = x3_mode(d);                                                 // split images (see x3_plan)
+  const bool ft = d->first_token != 0;
+  const int64_t ln = x3 ? R * 3 * D * 2 : R * D * es;
+  out[0] = R * D * xs;                                                        // x_in
+  out[1] = ln;                                                                // ln1
+  out[2] = ft ? R * D * es : R * 3 * D * es;                                  // qkv (first_token: V = O alone)
+  out[3] = ft ? 0 : x3 ? align256(R * D * 4) + R * 3 * D * 2 : R * D * es;    // o
+  out[4] = R * D * xs;                                                        // h
+  out[5] = ln;                                                                // ln2
+  out[6] = R * F * es;                                                        // pre
+  out[7] = x3 ? R * 3 * F * 2 : R * F * es;                                   // act
+  out[8] = out[9] = out[11] = out[12] = R * 4;                                // mean1, rstd1, mean2, rstd2
+  out[10] = ft ? 0 : (int64_t)d->B * d->H * d->N * 4;                         // lse
+  return CLIPMI_OK;
+}
 extern "C" int64_t clipmi_encoder_x3_ws(const clipmi_encoder_desc* d) { return d ? x3_bytes(d) : 0; }
 
 extern "C" int clipmi_encoder_fwd(void* s, const clipmi_encoder_desc* d) {
   CLIPMI_TRY(validate(d));
   const int dt = d->dtype;
-  const int R = d->B * d->N, D = d->D, F = d->F;
+  const int R = (int)rows(d), D = d->D, F = d->F;
   if (R == 0) return CLIPMI_OK;
   if (x3_mode(d)) return encoder_fwd_x3(s, d);
   if (dt == CLIPMI_FP8) {  // BASELINE config 5: frozen towers, MXFP8 GEMMs, bf16 everything else
@@ -480,9 +517,18 @@ extern "C" int clipmi_encoder_fwd(void* s, const clipmi_encoder_desc* d) {
     void* x_out = (l + 1 < d->L) ? d->act[l + 1].x_in : d->x_out;
     CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.x_in, D, a.ln1, D, w.ln1_w, w.ln1_b, a.mean1, a.rstd1, R, D, d->eps,
                                      nullptr, nullptr, 0));
-    CLIPMI_TRY(gemm(s, dt, R, 3 * D, D, a.ln1, D, true, w.qkv_w, D, true, a.qkv, 3 * D, dt, CLIPMI_EPI_BIAS, w.qkv_b));
-    CLIPMI_TRY(clipmi_attention_fwd(s, dt, a.qkv, a.o, a.lse, d->attention_mask, d->causal, d->B, d->H, d->N, D));
-    CLIPMI_TRY(gemm(s, dt, R, D, D, a.o, D, true, w.out_w, D, true, a.h, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
+    const void* o = a.o;
+    if (d->first_token) {  // token 0 sees one key, itself: O = V (0 where that key is padded), no q, k or softmax
+      const size_t es = esize(dt);
+      CLIPMI_TRY(gemm(s, dt, R, D, D, a.ln1, D, true, (const char*)w.qkv_w + (size_t)2 * D * D * es, D, true, a.qkv, D,
+                      dt, CLIPMI_EPI_BIAS, (const char*)w.qkv_b + (size_t)2 * D * es));
+      CLIPMI_TRY(select_rows(s, d, a.qkv));
+      o = a.qkv;
+    } else {
+      CLIPMI_TRY(gemm(s, dt, R, 3 * D, D, a.ln1, D, true, w.qkv_w, D, true, a.qkv, 3 * D, dt, CLIPMI_EPI_BIAS, w.qkv_b));
+      CLIPMI_TRY(clipmi_attention_fwd(s, dt, a.qkv, a.o, a.lse, d->attention_mask, d->causal, d->B, d->H, d->N, D));
+    }
+    CLIPMI_TRY(gemm(s, dt, R, D, D, o, D, true, w.out_w, D, true, a.h, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
                     w.out_b, a.x_in, D));
     CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.h, D, a.ln2, D, w.ln2_w, w.ln2_b, a.mean2, a.rstd2, R, D, d->eps,
                                      nullptr, nullptr, 0));
@@ -512,7 +558,7 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
   CLIPMI_REQUIRE(d->grads, "encoder_bwd needs gradient destinations");
   const int dt = d->dtype;
   const int xdt = (dt == CLIPMI_BF16 && d->resid_f32) ? CLIPMI_F32 : dt;  // the saved x_in / h
-  const int R = d->B * d->N, D = d->D, F = d->F;
+  const int R = (int)rows(d), D = d->D, F = d->F;
   if (R == 0) return CLIPMI_OK;
   if (x3_mode(d)) return encoder_bwd_x3(s, d, dx, layer_hi, layer_lo);
   const WsPlan p = plan(d);
@@ -588,13 +634,24 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
                                      g.ln2_b, 1, wln, ln_bytes, R, D));   // dh = dx + LN2'(d_ln2)
     // attention branch: g2 is dL/dh
     CLIPMI_TRY(gemm(s, dt, R, D, D, g2, D, true, w.out_w, D, false, dln, D, dt, 0));     // d_o = dh Wo
-    CLIPMI_TRY(wgrad(D, D, g2, D, a.o, D, g.out_w, g.out_b));                            // gWo += dh^T o
-    CLIPMI_TRY(clipmi_attention_bwd(s, dt, a.qkv, a.o, a.lse, dln, dbig, d->attention_mask, d->causal, d->B, d->H,
-                                    d->N, D));                              // d_qkv
-    CLIPMI_TRY(wgrad(3 * D, D, dbig, 3 * D, a.ln1, D, g.qkv_w, g.qkv_b));  // gWqkv += d_qkv^T ln1
-    CLIPMI_TRY(gemm(s, dt, R, D, 3 * D, dbig, 3 * D, true, w.qkv_w, D, false, dln, D, dt, 0));  // d_ln1
+    const void* dln1 = dln;
+    if (d->first_token) {  // O is V (act[l].qkv, row-selected): dV = d_o with the same select; the q / k slots of
+                           // gWqkv / gbqkv are left alone (their gradient is exactly zero)
+      CLIPMI_TRY(wgrad(D, D, g2, D, a.qkv, D, g.out_w, g.out_b));                        // gWo += dh^T o
+      CLIPMI_TRY(select_rows(s, d, dln));                                                 // dV
+      CLIPMI_TRY(wgrad(D, D, dln, D, a.ln1, D, g.qkv_w + (size_t)2 * D * D, g.qkv_b + 2 * D));  // gWv += dV^T ln1
+      CLIPMI_TRY(gemm(s, dt, R, D, D, dln, D, true, (const char*)w.qkv_w + (size_t)2 * D * D * esize(dt), D, false,
+                      dbig, D, dt, 0));                                                   // d_ln1 = dV Wv
+      dln1 = dbig;
+    } else {
+      CLIPMI_TRY(wgrad(D, D, g2, D, a.o, D, g.out_w, g.out_b));                          // gWo += dh^T o
+      CLIPMI_TRY(clipmi_attention_bwd(s, dt, a.qkv, a.o, a.lse, dln, dbig, d->attention_mask, d->causal, d->B, d->H,
+                                      d->N, D));                            // d_qkv
+      CLIPMI_TRY(wgrad(3 * D, D, dbig, 3 * D, a.ln1, D, g.qkv_w, g.qkv_b));  // gWqkv += d_qkv^T ln1
+      CLIPMI_TRY(gemm(s, dt, R, D, 3 * D, dbig, 3 * D, true, w.qkv_w, D, false, dln, D, dt, 0));  // d_ln1
+    }
     CLIPMI_TRY(ln_guard());
-    CLIPMI_TRY(clipmi_layernorm_bwd2(s, xdt, dt, dln, D, a.x_in, D, a.mean1, a.rstd1, w.ln1_w, dx, D, g2, D, g.ln1_w,
+    CLIPMI_TRY(clipmi_layernorm_bwd2(s, xdt, dt, dln1, D, a.x_in, D, a.mean1, a.rstd1, w.ln1_w, dx, D, g2, D, g.ln1_w,
                                      g.ln1_b, 1, wln, ln_bytes, R, D));    // dx_in = dh + LN1'(d_ln1)
   }
   if (pend.kind != 0) CLIPMI_TRY(launch_deferred((hipStream_t)s, pend));  // this call's gradients are final

@@ -1071,3 +1071,31 @@ extern "C" int clipmi_text_embed_bwd(void* stream, int dtype, const int64_t* ids
   CLIPMI_CHECK_LAUNCH();
   return CLIPMI_OK;
 }
+
+// ---- first-token encoder (engine.cpp): row r of x [R][D] is zeroed in place where keep[r * kstride] == 0 (the key
+// padding of token 0: a query whose only key is masked gets O = 0, as the attention kernels give a row with no
+// valid key); 16 B per lane, rows of D % (16 / element size) == 0 elements at 16-byte aligned addresses
+namespace {
+__global__ __launch_bounds__(256) void mask_rows_kernel(char* x, int64_t ld_bytes, int vecs, const int64_t* keep,
+                                                        int64_t kstride, int R) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r = i / vecs;
+  if (r >= R) return;
+  if (keep[r * kstride] != 0) return;
+  *(u32x4*)(x + r * ld_bytes + (i - r * vecs) * 16) = u32x4{0u, 0u, 0u, 0u};
+}
+}  // namespace
+
+int mask_rows(hipStream_t s, int dtype, void* x, int64_t ldx, int R, int D, const int64_t* keep, int64_t kstride) {
+  const int es = dtype == CLIPMI_F32 ? 4 : 2;
+  CLIPMI_REQUIRE(x && keep && R >= 0 && D > 0 && kstride >= 1, "mask_rows: arguments");
+  CLIPMI_REQUIRE((D * es) % 16 == 0 && (ldx * es) % 16 == 0 && ldx >= D && ((uintptr_t)x & 15) == 0,
+                 "mask_rows: rows must be whole 16-byte vectors");
+  if (R == 0) return CLIPMI_OK;
+  const int vecs = D * es / 16;
+  const int64_t total = (int64_t)R * vecs;
+  hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (char*)x, ldx * es, vecs,
+                     keep, kstride, R);
+  CLIPMI_CHECK_LAUNCH();
+  return CLIPMI_OK;
+}
