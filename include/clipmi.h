@@ -31,7 +31,8 @@ extern "C" {
 
 enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OCP e4m3 + E8M0 per 32 k */ };
 
-/* 2: clipmi_encoder_desc gained first_token (appended); clipmi_encoder_act_bytes */
+/* 2: clipmi_encoder_desc gained first_token (appended); clipmi_encoder_act_bytes
+ * 3: evaluation entry points (clipmi_rank_pick, clipmi_rank_count, clipmi_classify_accumulate) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -441,6 +442,34 @@ int clipmi_class_ce_bwd(void* stream, const float* dscore, const float* img, con
  * the shared cross-attention adapter's probabilities (adapter/clip_adapter.py:117). */
 int clipmi_softmax_rows(void* stream, const float* x, float* y, int R, int N, float scale);
 int clipmi_softmax_rows_bwd(void* stream, const float* y, const float* dy, float* dx, int R, int N, float scale);
+
+/* ---- Evaluation (csrc/eval.hip; clipmi_version() >= 3) -----------------------------------------
+ * Retrieval ranks of N queries against M candidates without the [N, M] score matrix (the recall@K /
+ * median-rank metrics of a dual encoder; the reference has none, its trainer.py:101-118 evaluate() is a mean
+ * batch loss).  The caller walks blocks S = Q[row0 : row0 + rows] . C[col0 : col0 + cols]^T (fp32, row stride
+ * lds >= cols, from clipmi_gemm) in a bounded scratch.  Query i's target candidate is target[i] (int64 [N]) or i
+ * when target == NULL (paired data, N == M).  Outputs are indexed by the global query row:
+ *   rank_pick   target_score[i] = S[i - row0][t_i - col0] for the rows whose target lies in the block's columns;
+ *   rank_count  greater[i] / equal[i] (+)= #{ j in the block, j != t_i : S[i, j] > / == target_score[i] } and
+ *               (top1[i], top1_score[i]) = the row maximum so far, lowest candidate index on ties; first != 0
+ *               (the row range's first block) stores instead of accumulating.
+ * Run rank_pick over every block that can hold a target before rank_count over all blocks, with the SAME
+ * clipmi_gemm call (shape, split_k) per block in both passes: the counts then compare target_score against the
+ * bits it was read from, so a duplicate of the target counts in `equal`, never in `greater`.  Blocks of one row
+ * range must be serialised on one stream (no atomics).  A target outside [0, M) sets *bad = 1 and leaves -1 in
+ * all five outputs of its row.  Row loads are 16-byte vectors when S is 16-byte aligned and lds % 4 == 0. */
+int clipmi_rank_pick(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols,
+                     const int64_t* target, float* target_score, int* bad);
+int clipmi_rank_count(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols,
+                      const int64_t* target, const float* target_score, int first, int* greater, int* equal,
+                      int* top1, float* top1_score);
+/* One batch of the reference's classification loops (evaluation.py:43-54, utils.py:48-61): pred[b] = argmax_c
+ * probs[b, c] (lowest index on ties), conf[b] its probability (torch.max(probs, 1)), and
+ * confusion[labels[b] * C + pred[b]] += 1 (int64 [C, C], rows = true class as sklearn's confusion_matrix;
+ * integer atomics, summed per workgroup first, so the result does not depend on the order).  A label outside
+ * [0, C) sets *bad = 1 and is not counted.  probs [B, C] fp32 contiguous, labels int64 [B]. */
+int clipmi_classify_accumulate(void* stream, const float* probs, const int64_t* labels, int B, int C, int* pred,
+                               float* conf, int64_t* confusion, int* bad);
 
 /* ---- Live kernel timing (bench.py roofline) --------------------------------------------------
  * While armed, every launch whose variant label is in the comma-separated list `variants`

@@ -20,4 +20,12 @@ def __getattr__(name):
     if name in ("CLIPAdapterTrainer", "FusedAdamW"):
         from . import trainer
         return getattr(trainer, name)
+    if name in _EVALUATION:  # on-device retrieval ranks and classification metrics
+        from . import evaluation
+        return getattr(evaluation, name)
     raise AttributeError(name)
+
+
+_EVALUATION = ("RankResult", "target_ranks", "recall_at_k", "rank_summary", "evaluate_retrieval",
+               "ClassificationMeter", "ClassificationResult", "classification_report", "accuracy", "evaluate_model",
+               "evaluate_enhanced_model")

@@ -1,0 +1,450 @@
+"""On-device evaluation: retrieval ranks for the contrastive model, classification metrics for the heads.
+
+Two families, both device-resident until one final transfer:
+
+* **Retrieval** (``target_ranks``, ``recall_at_k``, ``rank_summary``, ``evaluate_retrieval``): recall@K and
+  median / mean rank of ``CLIPWithAdapters`` over a whole validation set.  The reference has no such metric
+  (``trainer.evaluate()`` is a mean of per-batch losses, which depends on the batch size); the naive form needs
+  the [N, M] score matrix (40 GB of fp32 at N = 100k).  Here the scores are walked in ``block x block`` tiles of
+  the exact-f32 GEMM (``towers._gemm_f32``, the cosines the contrastive head trains on) and reduced by
+  csrc/eval.hip, so scratch is one tile.
+* **Classification** (``ClassificationMeter``, ``classification_report``, ``accuracy``, ``evaluate_model``,
+  ``evaluate_enhanced_model``): drop-ins for the reference's ``evaluation.evaluate_model`` (evaluation.py:17-68)
+  and ``utils.evaluate_enhanced_model`` (utils.py:24-68) without their four ``.cpu()`` round trips per batch and
+  without sklearn: argmax, confidence and the confusion matrix accumulate on the device
+  (``clipmi_classify_accumulate``), the report is formatted on the host from the confusion matrix in sklearn's
+  layout.
+
+One documented difference from the reference, shared by both ``evaluate_*`` functions: the confusion matrix
+always covers all C classes (utils.py:61 does the same with ``labels=range(C)``; evaluation.py:54 lets sklearn
+trim classes that occur neither as label nor as prediction, and its own ``classification_report`` call then
+raises on the name count).  Results are identical whenever every class occurs among the labels or predictions.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from dataclasses import dataclass
+from typing import Any, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import towers as T
+
+c_vp, c_int, c_i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+_lib.declare("clipmi_rank_pick", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_rank_count", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
+                                   c_vp, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_classify_accumulate", [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp])
+
+P_, call = T.P_, T.call
+
+EMOTIONS = ["angry", "disgust", "fear", "happy", "neutral", "sad", "surprise"]  # constants.EMOTIONS order
+
+
+# ------------------------------------------------------------------------------ retrieval
+@dataclass
+class RankResult:
+    """Per-query outputs of ``target_ranks`` (device tensors, length N).  With s = the scores of query i and
+    t = its target: ``target_score`` = s[t]; ``greater`` / ``equal`` = #{j != t: s[j] > / == s[t]};
+    ``top1`` / ``top1_score`` = argmax / max of s (lowest index on ties).  ``bad`` (int32 [1]) is non-zero when
+    a target was out of range; that row holds -1 everywhere."""
+    greater: Any
+    equal: Any
+    top1: Any = None
+    top1_score: Any = None
+    target_score: Any = None
+    bad: Any = None
+
+    def check(self):
+        """Raise IndexError if a target was out of range (one host synchronisation)."""
+        if self.bad is not None and int(torch.as_tensor(self.bad).reshape(-1)[0].item()):
+            raise IndexError("target_ranks: a target index is out of range [0, number of candidates)")
+        return self
+
+
+def eval_block():
+    """Rows and columns per score block (CLIPMI_EVAL_BLOCK, default 8192: a 256 MiB fp32 scratch)."""
+    return max(1, int(os.environ.get("CLIPMI_EVAL_BLOCK") or "8192"))
+
+
+def l2_normalize(x, out=None):
+    """Rows of x [B, E] (fp32, GPU) scaled to unit length by clipmi_l2norm_fwd, the contrastive head's kernel."""
+    x = x.to(torch.float32).contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    nrm = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    call("clipmi_l2norm_fwd", T.K.stream(), P_(x), P_(out), P_(nrm), x.shape[0], x.shape[1])
+    return out
+
+
+def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
+    """Rank statistics of each query's target among all candidates, scores = query @ candidates.T.
+
+    query [N, E], candidates [M, E]: fp32 GPU tensors, used as given (no normalisation, so integer-valued
+    inputs give exact scores).  target: int64 [N] candidate index per query, or None for paired data
+    (t_i = i, needs N == M).  block: rows and columns per GEMM block (default ``eval_block()``).
+
+    Memory: one block x block fp32 scratch plus five length-N outputs; no [N, M] buffer.  Each row range
+    walks its column blocks twice with the identical GEMM call: first to read the target scores out of the
+    GEMM output (blocks that cannot hold a target are skipped: with paired data only those on the
+    diagonal), then to count against them.  The bits of a score depend on the block shape (split-K is chosen
+    from it), so the target score is never taken from anywhere else: ties with a duplicate of the target are
+    exact.  No host synchronisation; ``RankResult.check()`` reports an out-of-range target."""
+    if query.dim() != 2 or candidates.dim() != 2 or query.shape[1] != candidates.shape[1]:
+        raise ValueError(f"target_ranks: query [N, E] and candidates [M, E], got {tuple(query.shape)} and "
+                         f"{tuple(candidates.shape)}")
+    if not (query.is_cuda and candidates.is_cuda):
+        raise ValueError("target_ranks needs GPU tensors (no CPU fallback)")
+    N, E = query.shape
+    M = candidates.shape[0]
+    if N <= 0 or M <= 0 or E <= 0:
+        raise ValueError("target_ranks: empty input")
+    dev = query.device
+    q = query.detach().to(torch.float32).contiguous()
+    c = candidates.detach().to(torch.float32).contiguous()
+    if target is None:
+        if N != M:
+            raise ValueError(f"target_ranks: paired data (target=None) needs N == M, got {N} and {M}")
+        tgt = None
+    else:
+        tgt = torch.as_tensor(target).detach().to(device=dev, dtype=torch.int64).contiguous()
+        if tgt.shape != (N,):
+            raise ValueError(f"target_ranks: target must have shape ({N},), got {tuple(tgt.shape)}")
+    blk = eval_block() if block is None else int(block)
+    if blk <= 0:
+        raise ValueError("target_ranks: block must be positive")
+    bm, bn = min(blk, N), min(blk, M)
+    sbuf = torch.empty(bm * bn, dtype=torch.float32, device=dev)
+    res = RankResult(greater=torch.empty(N, dtype=torch.int32, device=dev),
+                     equal=torch.empty(N, dtype=torch.int32, device=dev),
+                     top1=torch.empty(N, dtype=torch.int32, device=dev),
+                     top1_score=torch.empty(N, dtype=torch.float32, device=dev),
+                     target_score=torch.empty(N, dtype=torch.float32, device=dev),
+                     bad=torch.zeros(1, dtype=torch.int32, device=dev))
+    s = T.K.stream()
+    cblocks = [(c0, min(blk, M - c0)) for c0 in range(0, M, blk)]
+
+    def scores(r0, rows, c0, cols):
+        T._gemm_f32(rows, cols, E, q[r0:], E, True, c[c0:], E, True, sbuf, cols)
+
+    for r0 in range(0, N, blk):
+        rows = min(blk, N - r0)
+        for c0, cols in cblocks:
+            if tgt is None and (c0 >= r0 + rows or c0 + cols <= r0):
+                continue  # paired: no t_i = i of these rows lies in these columns
+            scores(r0, rows, c0, cols)
+            call("clipmi_rank_pick", s, P_(sbuf), cols, N, M, r0, rows, c0, cols, P_(tgt), P_(res.target_score),
+                 P_(res.bad))
+        for n, (c0, cols) in enumerate(cblocks):
+            if len(cblocks) > 1:  # a single column block is still in the scratch from the first pass
+                scores(r0, rows, c0, cols)
+            call("clipmi_rank_count", s, P_(sbuf), cols, N, M, r0, rows, c0, cols, P_(tgt), P_(res.target_score),
+                 1 if n == 0 else 0, P_(res.greater), P_(res.equal), P_(res.top1), P_(res.top1_score))
+    return res
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _ranks(result, ties):
+    """1-based ranks (int64 numpy) under a tie policy; a device-resident result is checked and copied here."""
+    if ties not in ("optimistic", "pessimistic"):
+        raise ValueError(f"ties must be 'optimistic' or 'pessimistic', got {ties!r}")
+    if isinstance(result, RankResult):
+        result.check()
+    rank = _host(result.greater).astype(np.int64) + 1
+    if ties == "pessimistic":
+        rank = rank + _host(result.equal).astype(np.int64)
+    return rank
+
+
+def recall_at_k(result, ks=(1, 5, 10), ties="optimistic"):
+    """{k: fraction of queries whose target ranks within the top k}.
+
+    ``optimistic`` rank = greater + 1 (the target wins every tie); ``pessimistic`` rank = greater + equal + 1.
+    Optimistic is the default because this project's data repeats captions (35 captions over thousands of
+    images, dataset.py:13-63): the candidates then hold exact duplicates of the positive, every duplicate
+    scores bit-equal to it, and retrieving any of them is a correct retrieval.  Counting them against the
+    positive would cap R@1 near 35 / N whatever the model does.  Ties between distinct candidates are
+    measure-zero in fp32 cosines, so the two policies differ by the duplicates alone."""
+    rank = _ranks(result, ties)
+    return {int(k): float(np.mean(rank <= int(k))) for k in ks}
+
+
+def rank_summary(result, ties="optimistic"):
+    """{"median_rank", "mean_rank"}: 1-based, under the same tie policies as ``recall_at_k``."""
+    rank = _ranks(result, ties)
+    return {"median_rank": float(np.median(rank)), "mean_rank": float(np.mean(rank))}
+
+
+class _Rows:
+    """A growing [n, ...] device buffer: preallocated when the total is known, doubled on demand otherwise."""
+
+    def __init__(self, tail, dtype, device, capacity):
+        self.buf = torch.empty((max(int(capacity), 1),) + tuple(tail), dtype=dtype, device=device)
+        self.n = 0
+
+    def take(self, b):
+        """-> the next b rows (a contiguous view to write into)."""
+        need = self.n + b
+        if need > self.buf.shape[0]:
+            grown = torch.empty((max(2 * self.buf.shape[0], need),) + tuple(self.buf.shape[1:]),
+                                dtype=self.buf.dtype, device=self.buf.device)
+            grown[:self.n].copy_(self.buf[:self.n])
+            self.buf = grown
+        view = self.buf[self.n:need]
+        self.n = need
+        return view
+
+    def rows(self):
+        return self.buf[:self.n]
+
+
+def _dataset_len(loader):
+    try:
+        return len(loader.dataset)
+    except (AttributeError, TypeError):
+        return 0
+
+
+def evaluate_retrieval(model, dataloader, ks=(1, 5, 10), block=None):
+    """Image->text and text->image retrieval of a ``CLIPWithAdapters`` over a whole dataloader.
+
+    Eval mode under no_grad; per batch ``model(..., return_loss=False)``, features L2-normalised by
+    clipmi_l2norm_fwd into device buffers (sized from ``len(dataloader.dataset)`` when there is one); nothing
+    inside the loop synchronises with the host.  Pair i is (image i, caption i).  Returns ``n``,
+    ``i2t_R@k`` / ``t2i_R@k`` for k in ks, ``{i2t,t2i}_median_rank``, ``{i2t,t2i}_mean_rank`` (optimistic
+    ties, see ``recall_at_k``) and the two ``RankResult``s under ``i2t`` / ``t2i``.  The model's train / eval
+    mode is restored."""
+    was_training = model.training
+    device = model.clip.arena.device
+    total = _dataset_len(dataloader)
+    txt = img = None
+    model.eval()
+    try:
+        with torch.no_grad():
+            for batch in dataloader:
+                batch = {k: v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v
+                         for k, v in batch.items()}
+                out = model(input_ids=batch.get("input_ids"), attention_mask=batch.get("attention_mask"),
+                            pixel_values=batch.get("pixel_values"), return_loss=False)
+                tf, imf = out["text_features"], out["image_features"]
+                if tf is None or imf is None:
+                    raise ValueError("evaluate_retrieval: every batch needs input_ids and pixel_values")
+                if txt is None:
+                    txt = _Rows((tf.shape[1],), torch.float32, device, total)
+                    img = _Rows((imf.shape[1],), torch.float32, device, total)
+                l2_normalize(tf, out=txt.take(tf.shape[0]))
+                l2_normalize(imf, out=img.take(imf.shape[0]))
+            if txt is None:
+                raise ValueError("evaluate_retrieval: the dataloader is empty")
+            i2t = target_ranks(img.rows(), txt.rows(), None, block=block)
+            t2i = target_ranks(txt.rows(), img.rows(), None, block=block)
+    finally:
+        model.train(was_training)
+    res = {"n": txt.n}
+    for name, r in (("i2t", i2t), ("t2i", t2i)):
+        on_host = RankResult(greater=_host(r.check().greater), equal=None)  # optimistic ties read `greater` alone
+        for k, v in recall_at_k(on_host, ks).items():
+            res[f"{name}_R@{k}"] = v
+        for k, v in rank_summary(on_host).items():
+            res[f"{name}_{k}"] = v
+    res["i2t"], res["t2i"] = i2t, t2i
+    return res
+
+
+# ------------------------------------------------------------------------------ classification
+@dataclass
+class ClassificationResult:
+    """Host copies (numpy) of a ``ClassificationMeter``: confusion int64 [C, C] (rows = true class), preds
+    int64 [n], confidences float32 [n], labels int64 [n], probs float32 [n, C]."""
+    confusion: np.ndarray
+    preds: np.ndarray
+    confidences: np.ndarray
+    labels: np.ndarray
+    probs: np.ndarray
+
+
+class ClassificationMeter:
+    """Device-resident tallies of a classification run: per batch ``update(probs, labels)`` takes the row
+    argmax (lowest index on ties) and its probability, exactly ``torch.max(probs, 1)``, and adds the batch into
+    the [C, C] confusion matrix, all in clipmi_classify_accumulate without a host synchronisation;
+    ``result()`` makes one transfer."""
+
+    def __init__(self, num_classes, capacity=0):
+        if int(num_classes) <= 0:
+            raise ValueError("ClassificationMeter: num_classes must be positive")
+        self.C = int(num_classes)
+        self._capacity = int(capacity)
+        self.confusion = None
+
+    def _alloc(self, device):
+        C, cap = self.C, self._capacity
+        self.confusion = torch.zeros(C, C, dtype=torch.int64, device=device)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=device)
+        self.pred = _Rows((), torch.int32, device, cap)
+        self.conf = _Rows((), torch.float32, device, cap)
+        self.label = _Rows((), torch.int64, device, cap)
+        self.probs = _Rows((C,), torch.float32, device, cap)
+
+    @property
+    def n(self):
+        return 0 if self.confusion is None else self.pred.n
+
+    def update(self, probs, labels):
+        if probs.dim() != 2 or probs.shape[1] != self.C:
+            raise ValueError(f"ClassificationMeter: probs must be [B, {self.C}], got {tuple(probs.shape)}")
+        if not probs.is_cuda:
+            raise ValueError("ClassificationMeter needs GPU probabilities (no CPU fallback)")
+        B = probs.shape[0]
+        labels = torch.as_tensor(labels)
+        if labels.shape != (B,):
+            raise ValueError(f"ClassificationMeter: labels must have shape ({B},), got {tuple(labels.shape)}")
+        if B == 0:
+            return
+        if self.confusion is None:
+            self._alloc(probs.device)
+        p, lab = self.probs.take(B), self.label.take(B)
+        p.copy_(probs.detach())
+        lab.copy_(labels.detach(), non_blocking=True)
+        call("clipmi_classify_accumulate", T.K.stream(), P_(p), P_(lab), B, self.C, P_(self.pred.take(B)),
+             P_(self.conf.take(B)), P_(self.confusion), P_(self.bad))
+
+    def result(self) -> ClassificationResult:
+        """One device-to-host transfer of everything; IndexError if a label was outside [0, C)."""
+        C = self.C
+        if self.confusion is None:
+            return ClassificationResult(np.zeros((C, C), np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32),
+                                        np.zeros(0, np.int64), np.zeros((0, C), np.float32))
+        n = self.pred.n
+        parts = [self.confusion, self.label.rows(), self.bad, self.pred.rows(), self.conf.rows(), self.probs.rows()]
+        blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+        out, off = [], 0
+        for t, dtype in zip(parts, (np.int64, np.int64, np.int32, np.int32, np.float32, np.float32)):
+            out.append(np.frombuffer(blob, dtype=dtype, count=t.numel(), offset=off).copy())
+            off += t.numel() * t.element_size()
+        conf_matrix, lab, bad, pred, conf, probs = out
+        if int(bad[0]):
+            raise IndexError(f"ClassificationMeter: a label is out of range [0, {C})")
+        return ClassificationResult(conf_matrix.reshape(C, C), pred.astype(np.int64), conf, lab, probs.reshape(n, C))
+
+
+def accuracy(confusion):
+    """Fraction of samples on the diagonal (sklearn accuracy_score of the same labels and predictions)."""
+    cm = np.asarray(confusion, dtype=np.int64)
+    total = int(cm.sum())
+    return float(np.trace(cm)) / total if total else 0.0
+
+
+def _div(num, den):
+    """num / den with zero_division=0."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.divide(num, den, out=np.zeros_like(num), where=den != 0)
+
+
+def classification_report(confusion, target_names, digits=4):
+    """sklearn.metrics.classification_report(labels, preds, target_names=..., digits=..., zero_division=0) as a
+    string, computed from the confusion matrix (rows = true class) over all C classes: per class precision,
+    recall, f1-score and support, then accuracy, macro avg and weighted avg."""
+    cm = np.asarray(confusion, dtype=np.int64)
+    C = cm.shape[0]
+    if cm.shape != (C, C) or len(target_names) != C:
+        raise ValueError(f"classification_report: a [C, C] confusion matrix and C names, got {cm.shape} and "
+                         f"{len(target_names)}")
+    tp = np.diag(cm).astype(np.float64)
+    support = cm.sum(1)
+    pred_sum = cm.sum(0)
+    p, r = _div(tp, pred_sum), _div(tp, support)
+    f1 = _div(2 * tp, support + pred_sum)
+    total = int(support.sum())
+    headers = ["precision", "recall", "f1-score", "support"]
+    width = max(max(len(str(n)) for n in target_names), len("weighted avg"), digits)
+    report = ("{:>{width}s} " + " {:>9}" * len(headers)).format("", *headers, width=width) + "\n\n"
+    row_fmt = "{:>{width}s} " + " {:>9.{digits}f}" * 3 + " {:>9}\n"
+    for row in zip(target_names, p, r, f1, support):
+        report += row_fmt.format(str(row[0]), *row[1:], width=width, digits=digits)
+    report += "\n"
+    report += ("{:>{width}s} " + " {:>9.{digits}}" * 2 + " {:>9.{digits}f}" + " {:>9}\n").format(
+        "accuracy", "", "", accuracy(cm), total, width=width, digits=digits)
+    report += row_fmt.format("macro avg", p.mean(), r.mean(), f1.mean(), total, width=width, digits=digits)
+    w = _div(support, total)
+    report += row_fmt.format("weighted avg", (p * w).sum(), (r * w).sum(), (f1 * w).sum(), total, width=width,
+                             digits=digits)
+    return report
+
+
+def _cuda():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _eval_mode(*mods):
+    for m in mods:
+        if m is not None and hasattr(m, "eval"):
+            m.eval()
+
+
+def _finish(meter, target_names):
+    r = meter.result()
+    return (accuracy(r.confusion), r.confusion, classification_report(r.confusion, target_names, digits=4),
+            list(r.preds), list(r.labels), list(r.confidences), r.probs)
+
+
+def evaluate_model(model, test_loader, use_all_descriptions=False):
+    """evaluation.evaluate_model (evaluation.py:17-68) for ``heads.CLIPAdapter`` /
+    ``heads.ZeroShotEmotionRecognition``: the same 8-tuple (accuracy, conf_matrix, class_report, all_preds,
+    all_labels, all_image_paths, all_confidences, all_similarity_scores) over ``predict`` or
+    ``predict_with_all_descriptions``.  The loader yields (pixel_values, labels, img_paths).  The report's class
+    names are the model's description keys (constants.EMOTIONS order, see heads.py), else constants.EMOTIONS."""
+    _eval_mode(getattr(model, "model", None), getattr(model, "visual_adapter", None),
+               getattr(model, "text_adapter", None))
+    descs = getattr(model, "emotion_descriptions", None)
+    target_names = list(descs.keys()) if descs else EMOTIONS
+    meter, paths = None, []
+    with torch.no_grad():
+        for pixel_values, labels, img_paths in test_loader:
+            pixel_values = pixel_values.to(_cuda(), non_blocking=True)
+            if use_all_descriptions and hasattr(model, "predict_with_all_descriptions"):
+                probs = model.predict_with_all_descriptions(pixel_values)
+            else:
+                probs = model.predict(pixel_values)
+            if meter is None:
+                meter = ClassificationMeter(probs.shape[1], _dataset_len(test_loader))
+            meter.update(probs, labels)
+            if img_paths is not None:
+                paths.extend(img_paths)
+    if meter is None:
+        raise ValueError("evaluate_model: the loader is empty")
+    acc, cm, report, preds, labs, confs, probs = _finish(meter, target_names)
+    return acc, cm, report, preds, labs, paths, confs, probs
+
+
+def evaluate_enhanced_model(model, test_loader, emotions=EMOTIONS):
+    """utils.evaluate_enhanced_model (utils.py:24-68) for ``heads.EnhancedCLIPAdapter``: the same 9-tuple
+    (accuracy, conf_matrix, class_report, all_preds, all_labels, all_image_paths, all_confidences,
+    all_similarity_scores, all_contexts_text) over ``predict_probs``.  The loader yields (pixel_values, labels,
+    img_paths, context_features, contexts_text)."""
+    model.eval()
+    C = len(emotions)
+    meter = ClassificationMeter(C, _dataset_len(test_loader))
+    paths, contexts = [], []
+    with torch.no_grad():
+        for pixel_values, labels, img_paths, context_features, contexts_text in test_loader:
+            dev = _cuda()
+            pixel_values = pixel_values.to(dev, non_blocking=True)
+            if isinstance(context_features, list):
+                context_features = torch.stack(context_features)
+            if context_features is not None:
+                context_features = context_features.to(dev, non_blocking=True)
+            meter.update(model.predict_probs(pixel_values, context_features), labels)
+            if img_paths is not None:
+                paths.extend(img_paths)
+            if contexts_text is not None:
+                contexts.extend(contexts_text)
+    if meter.n == 0:  # utils.py:58-62 on an empty loader
+        return 0.0, np.zeros((C, C)), "No data to report.", [], [], paths, [], np.array([]), contexts
+    acc, cm, report, preds, labs, confs, probs = _finish(meter, list(emotions))
+    return acc, cm, report, preds, labs, paths, confs, probs, contexts
