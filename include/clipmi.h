@@ -124,7 +124,10 @@ int clipmi_quant_mxfp8(void* stream, int dtype, const void* x, int64_t ldx, int6
  * y = LN(x [+ pos[row % period] (+ cls at row % period == 0)]) * w + b; mean/rstd saved (fp32).
  * With pos != NULL the sum is written back to x: the vision embedding ([HF] :209-219) fused
  * into pre_layrnorm. Weights in the activation dtype. 1 <= D <= 4096: register-resident kernels for D / 64
- * in {1, 2, 3, 4, 6, 8, 12, 16} (every CLIP width), a one-wave-per-row kernel for any other width. */
+ * in {1, 2, 3, 4, 6, 8, 12, 16} (every CLIP width), a one-wave-per-row kernel for any other width.  Leading
+ * dimensions (>= D) and base pointers need no alignment beyond the element's: the register-resident kernels move
+ * pieces of 4 (D % 256 == 0), 2 (D % 128 == 0) or 1 elements as one vector, and a call whose pointers or leading
+ * dimensions are no multiple of that piece runs the one-wave-per-row kernel instead (forward and backward). */
 int clipmi_layernorm_fwd(void* stream, int dtype, void* x, int64_t ldx, void* y, int64_t ldy, const void* w,
                          const void* b, float* mean, float* rstd, int R, int D, float eps, const void* pos,
                          const void* cls, int period);

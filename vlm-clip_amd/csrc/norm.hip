@@ -745,6 +745,18 @@ inline bool ln_fast_width(int D) {
   return q == 1 || q == 2 || q == 3 || q == 4 || q == 6 || q == 8 || q == 12 || q == 16;
 }
 
+// The register-resident kernels move a row in pieces of PS elements (the PS of LN_DISPATCH below) as one vector
+// access each: a row base or a leading dimension that is no multiple of PS elements sends the call to the
+// one-wave-per-row kernel, which has no such need.
+inline int ln_ps(int D) {
+  const int q = D / 64;
+  return q % 4 == 0 ? 4 : q % 2 == 0 ? 2 : 1;
+}
+template <typename T>
+inline bool ln_aligned(const void* p, int64_t ld, int ps) {
+  return (uintptr_t)p % (ps * sizeof(T)) == 0 && ld % ps == 0;
+}
+
 // dispatch on (PS, NP) from D
 // (TX: the normalised input x; T: everything else -- output / gradients / affine weights)
 #define LN_DISPATCH(D, FN, TX, T, ...)                                          \
@@ -774,7 +786,10 @@ static int ln_types_ok(int x_dtype, int dtype) {
 template <typename TX, typename T>
 static int ln_fwd_t(hipStream_t s, void* x, int64_t ldx, void* y, int64_t ldy, const void* w, const void* b, float* mean,
                     float* rstd, int R, int D, float eps, const void* pos, const void* cls, int period) {
-  if (!ln_fast_width(D)) {  // any other width: the one-wave-per-row kernel
+  const int ps = ln_ps(D);
+  const bool vec = ln_aligned<TX>(x, ldx, ps) && ln_aligned<T>(y, ldy, ps) && ln_aligned<T>(w, 0, ps) &&
+                   ln_aligned<T>(b, 0, ps) && ln_aligned<TX>(pos, 0, ps) && ln_aligned<TX>(cls, 0, ps);
+  if (!ln_fast_width(D) || !vec) {  // any other width or alignment: the one-wave-per-row kernel
     hipLaunchKernelGGL((ln_fwd_any_kernel<TX, T>), dim3((R + 3) / 4), dim3(256), 0, s, (TX*)x, ldx, (T*)y, ldy,
                        (const T*)w, (const T*)b, mean, rstd, R, D, eps, (const TX*)pos, (const TX*)cls, period);
     return CLIPMI_OK;
@@ -841,7 +856,10 @@ template <typename TX, typename T, typename TW = T>
 static int ln_bwd_t(hipStream_t s, int& nb, const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* mean,
                     const float* rstd, const void* w, void* dx, int64_t lddx, const void* dres, int64_t ldres, float* wsf,
                     int R, int D) {
-  if (!ln_fast_width(D)) {
+  const int ps = ln_ps(D);
+  const bool vec = ln_aligned<T>(dy, lddy, ps) && ln_aligned<TX>(x, ldx, ps) && ln_aligned<TW>(w, 0, ps) &&
+                   ln_aligned<T>(dx, lddx, ps) && (!dres || ln_aligned<T>(dres, ldres, ps));
+  if (!ln_fast_width(D) || !vec) {
     const size_t lds = wsf ? (size_t)4 * 2 * D * 4 : 0;
     (void)lds_optin((const void*)ln_bwd_any_kernel<TX, T, TW>, (int)lds);
     hipLaunchKernelGGL((ln_bwd_any_kernel<TX, T, TW>), dim3(nb), dim3(256), lds, s, (const T*)dy, lddy, (const TX*)x, ldx,
