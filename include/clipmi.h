@@ -32,7 +32,8 @@ extern "C" {
 enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OCP e4m3 + E8M0 per 32 k */ };
 
 /* 2: clipmi_encoder_desc gained first_token (appended); clipmi_encoder_act_bytes
- * 3: evaluation entry points (clipmi_rank_pick, clipmi_rank_count, clipmi_classify_accumulate) */
+ * 3: evaluation entry points (clipmi_rank_pick, clipmi_rank_count, clipmi_classify_accumulate)
+ * 4: clipmi_topk_merge */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -466,6 +467,22 @@ int clipmi_rank_pick(void* stream, const float* S, int64_t lds, int N, int M, in
 int clipmi_rank_count(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols,
                       const int64_t* target, const float* target_score, int first, int* greater, int* equal,
                       int* top1, float* top1_score);
+/* Top-K retrieval over the same streamed blocks (csrc/topk.hip; clipmi_version() >= 4): after the call, rows
+ * row0 .. row0 + rows - 1 of top_score / top_idx ([N, k] contiguous, indexed by the global query row) hold the k
+ * best candidates of every block merged so far, best first.  S, lds, N, M and the block ranges are as for
+ * clipmi_rank_count.  The order is strict and total: candidate a precedes b iff s_a > s_b, or s_a == s_b and
+ * j_a < j_b, with -0.0 == +0.0 (reported as +0.0); scores are expected to be finite, a NaN is ordered and
+ * reported as -inf.  The result therefore does not depend on the block size or on the order of the column
+ * blocks, given equal score bits.  first != 0 starts the row range's lists from empty, otherwise the block is
+ * merged into the lists already in the outputs.  Slots beyond the number of candidates seen hold idx -1 and
+ * score -inf.  exclude (int64 [N] or NULL): candidate exclude[i] never enters query i's list (the positive, for
+ * hard-negative mining; pass it with every block); a value outside [0, M) excludes nothing.
+ * 1 <= k <= CLIPMI_TOPK_MAX.  Rows outside the block's row range are not touched.  Blocks of one row range must
+ * be serialised on one stream (no atomics); nothing is allocated or synchronised.  Row loads are 16-byte
+ * vectors when S is 16-byte aligned and lds % 4 == 0. */
+#define CLIPMI_TOPK_MAX 256
+int clipmi_topk_merge(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols,
+                      int k, int first, const int64_t* exclude, float* top_score, int* top_idx);
 /* One batch of the reference's classification loops (evaluation.py:43-54, utils.py:48-61): pred[b] = argmax_c
  * probs[b, c] (lowest index on ties), conf[b] its probability (torch.max(probs, 1)), and
  * confusion[labels[b] * C + pred[b]] += 1 (int64 [C, C], rows = true class as sklearn's confusion_matrix;

@@ -26,6 +26,6 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
-_EVALUATION = ("RankResult", "target_ranks", "recall_at_k", "rank_summary", "evaluate_retrieval",
+_EVALUATION = ("RankResult", "target_ranks", "TopK", "topk", "recall_at_k", "rank_summary", "evaluate_retrieval",
                "ClassificationMeter", "ClassificationResult", "classification_report", "accuracy", "evaluate_model",
                "evaluate_enhanced_model")

@@ -7,7 +7,8 @@ Two families, both device-resident until one final transfer:
   (``trainer.evaluate()`` is a mean of per-batch losses, which depends on the batch size); the naive form needs
   the [N, M] score matrix (40 GB of fp32 at N = 100k).  Here the scores are walked in ``block x block`` tiles of
   the exact-f32 GEMM (``towers._gemm_f32``, the cosines the contrastive head trains on) and reduced by
-  csrc/eval.hip, so scratch is one tile.
+  csrc/eval.hip, so scratch is one tile.  ``topk`` keeps each query's k best candidates over the same tiles
+  (csrc/topk.hip): which candidates were retrieved, or with ``exclude`` the hardest negatives.
 * **Classification** (``ClassificationMeter``, ``classification_report``, ``accuracy``, ``evaluate_model``,
   ``evaluate_enhanced_model``): drop-ins for the reference's ``evaluation.evaluate_model`` (evaluation.py:17-68)
   and ``utils.evaluate_enhanced_model`` (utils.py:24-68) without their four ``.cpu()`` round trips per batch and
@@ -38,6 +39,8 @@ _lib.declare("clipmi_rank_pick", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int,
 _lib.declare("clipmi_rank_count", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int,
                                    c_vp, c_vp, c_vp, c_vp])
 _lib.declare("clipmi_classify_accumulate", [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_topk_merge", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                   c_vp, c_vp])
 
 P_, call = T.P_, T.call
 
@@ -80,6 +83,25 @@ def l2_normalize(x, out=None):
     return out
 
 
+def _score_operands(who, query, candidates):
+    """The argument checks shared by the block walks: -> (query, candidates) as contiguous fp32."""
+    if query.dim() != 2 or candidates.dim() != 2 or query.shape[1] != candidates.shape[1]:
+        raise ValueError(f"{who}: query [N, E] and candidates [M, E], got {tuple(query.shape)} and "
+                         f"{tuple(candidates.shape)}")
+    if not (query.is_cuda and candidates.is_cuda):
+        raise ValueError(f"{who} needs GPU tensors (no CPU fallback)")
+    if query.shape[0] <= 0 or candidates.shape[0] <= 0 or query.shape[1] <= 0:
+        raise ValueError(f"{who}: empty input")
+    return query.detach().to(torch.float32).contiguous(), candidates.detach().to(torch.float32).contiguous()
+
+
+def _block_size(who, block):
+    blk = eval_block() if block is None else int(block)
+    if blk <= 0:
+        raise ValueError(f"{who}: block must be positive")
+    return blk
+
+
 def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
     """Rank statistics of each query's target among all candidates, scores = query @ candidates.T.
 
@@ -93,18 +115,8 @@ def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
     diagonal), then to count against them.  The bits of a score depend on the block shape (split-K is chosen
     from it), so the target score is never taken from anywhere else: ties with a duplicate of the target are
     exact.  No host synchronisation; ``RankResult.check()`` reports an out-of-range target."""
-    if query.dim() != 2 or candidates.dim() != 2 or query.shape[1] != candidates.shape[1]:
-        raise ValueError(f"target_ranks: query [N, E] and candidates [M, E], got {tuple(query.shape)} and "
-                         f"{tuple(candidates.shape)}")
-    if not (query.is_cuda and candidates.is_cuda):
-        raise ValueError("target_ranks needs GPU tensors (no CPU fallback)")
-    N, E = query.shape
-    M = candidates.shape[0]
-    if N <= 0 or M <= 0 or E <= 0:
-        raise ValueError("target_ranks: empty input")
-    dev = query.device
-    q = query.detach().to(torch.float32).contiguous()
-    c = candidates.detach().to(torch.float32).contiguous()
+    q, c = _score_operands("target_ranks", query, candidates)
+    (N, E), M, dev = q.shape, c.shape[0], q.device
     if target is None:
         if N != M:
             raise ValueError(f"target_ranks: paired data (target=None) needs N == M, got {N} and {M}")
@@ -113,9 +125,7 @@ def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
         tgt = torch.as_tensor(target).detach().to(device=dev, dtype=torch.int64).contiguous()
         if tgt.shape != (N,):
             raise ValueError(f"target_ranks: target must have shape ({N},), got {tuple(tgt.shape)}")
-    blk = eval_block() if block is None else int(block)
-    if blk <= 0:
-        raise ValueError("target_ranks: block must be positive")
+    blk = _block_size("target_ranks", block)
     bm, bn = min(blk, N), min(blk, M)
     sbuf = torch.empty(bm * bn, dtype=torch.float32, device=dev)
     res = RankResult(greater=torch.empty(N, dtype=torch.int32, device=dev),
@@ -144,6 +154,62 @@ def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
             call("clipmi_rank_count", s, P_(sbuf), cols, N, M, r0, rows, c0, cols, P_(tgt), P_(res.target_score),
                  1 if n == 0 else 0, P_(res.greater), P_(res.equal), P_(res.top1), P_(res.top1_score))
     return res
+
+
+TOPK_MAX = 256  # CLIPMI_TOPK_MAX of include/clipmi.h
+
+
+@dataclass
+class TopK:
+    """Per-query outputs of ``topk`` (device tensors): ``scores`` fp32 [N, k] and ``indices`` int32 [N, k], each
+    row sorted best first (higher score first, lower candidate index on equal scores) and padded with -inf / -1
+    where fewer than k candidates exist."""
+    scores: Any
+    indices: Any
+
+
+def topk(query, candidates, k, *, exclude=None, block=None) -> TopK:
+    """The k best candidates of every query, scores = query @ candidates.T, without the [N, M] score matrix.
+
+    query [N, E], candidates [M, E] and block are as for ``target_ranks``: the same exact-f32 GEMM call per block,
+    so a score here has the bits the rank kernels compare (``indices[:, 0]`` is ``RankResult.top1``, and a
+    target with ``greater + equal < k`` is in the list).  1 <= k <= 256.  exclude: int64 [N], a candidate index
+    per query that never enters its list (the positive, for hard-negative mining); values outside [0, M)
+    exclude nothing.  The order is total (ties go to the lower index; -0.0 == +0.0; scores are expected to be
+    finite, a NaN is ordered and reported as -inf), so the result does not depend on ``block`` beyond the bits of
+    the GEMM output.
+
+    One pass over the blocks, each merged into the running lists by clipmi_topk_merge; memory is one
+    block x block fp32 scratch plus the two [N, k] outputs; no host synchronisation."""
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"topk: k must be in [1, {TOPK_MAX}], got {k}")
+    ex = None
+    if exclude is not None:
+        ex = torch.as_tensor(exclude)
+        if query.dim() == 2 and ex.shape != (query.shape[0],):
+            raise ValueError(f"topk: exclude must have shape ({query.shape[0]},), got {tuple(ex.shape)}")
+    q, c = _score_operands("topk", query, candidates)
+    (N, E), M, dev = q.shape, c.shape[0], q.device
+    if ex is not None:
+        ex = ex.detach().to(device=dev, dtype=torch.int64).contiguous()
+    blk = _block_size("topk", block)
+    bm, bn = min(blk, N), min(blk, M)
+    sbuf = torch.empty(bm * bn, dtype=torch.float32, device=dev)
+    res = TopK(scores=torch.empty(N, k, dtype=torch.float32, device=dev),
+               indices=torch.empty(N, k, dtype=torch.int32, device=dev))
+    s = T.K.stream()
+    for r0 in range(0, N, blk):
+        rows = min(blk, N - r0)
+        for c0 in range(0, M, blk):
+            cols = min(blk, M - c0)
+            T._gemm_f32(rows, cols, E, q[r0:], E, True, c[c0:], E, True, sbuf, cols)
+            call("clipmi_topk_merge", s, P_(sbuf), cols, N, M, r0, rows, c0, cols, k, 1 if c0 == 0 else 0, P_(ex),
+                 P_(res.scores), P_(res.indices))
+    return res
+
+
+_topk = topk  # evaluate_retrieval's `topk` keyword shadows the function
 
 
 def _host(x):
@@ -211,15 +277,20 @@ def _dataset_len(loader):
         return 0
 
 
-def evaluate_retrieval(model, dataloader, ks=(1, 5, 10), block=None):
+def evaluate_retrieval(model, dataloader, ks=(1, 5, 10), block=None, topk=0):
     """Image->text and text->image retrieval of a ``CLIPWithAdapters`` over a whole dataloader.
 
     Eval mode under no_grad; per batch ``model(..., return_loss=False)``, features L2-normalised by
     clipmi_l2norm_fwd into device buffers (sized from ``len(dataloader.dataset)`` when there is one); nothing
     inside the loop synchronises with the host.  Pair i is (image i, caption i).  Returns ``n``,
     ``i2t_R@k`` / ``t2i_R@k`` for k in ks, ``{i2t,t2i}_median_rank``, ``{i2t,t2i}_mean_rank`` (optimistic
-    ties, see ``recall_at_k``) and the two ``RankResult``s under ``i2t`` / ``t2i``.  The model's train / eval
-    mode is restored."""
+    ties, see ``recall_at_k``) and the two ``RankResult``s under ``i2t`` / ``t2i``.  With topk > 0 the result
+    also carries the ``topk`` best captions of every image and images of every caption as ``TopK`` objects under
+    ``i2t_topk`` / ``t2i_topk``; with the default it has exactly the keys above.  The model's train / eval mode is
+    restored."""
+    topk = int(topk)
+    if topk < 0 or topk > TOPK_MAX:
+        raise ValueError(f"evaluate_retrieval: topk must be in [0, {TOPK_MAX}], got {topk}")
     was_training = model.training
     device = model.clip.arena.device
     total = _dataset_len(dataloader)
@@ -244,6 +315,9 @@ def evaluate_retrieval(model, dataloader, ks=(1, 5, 10), block=None):
                 raise ValueError("evaluate_retrieval: the dataloader is empty")
             i2t = target_ranks(img.rows(), txt.rows(), None, block=block)
             t2i = target_ranks(txt.rows(), img.rows(), None, block=block)
+            if topk:
+                i2t_top = _topk(img.rows(), txt.rows(), topk, block=block)
+                t2i_top = _topk(txt.rows(), img.rows(), topk, block=block)
     finally:
         model.train(was_training)
     res = {"n": txt.n}
@@ -254,6 +328,8 @@ def evaluate_retrieval(model, dataloader, ks=(1, 5, 10), block=None):
         for k, v in rank_summary(on_host).items():
             res[f"{name}_{k}"] = v
     res["i2t"], res["t2i"] = i2t, t2i
+    if topk:
+        res["i2t_topk"], res["t2i_topk"] = i2t_top, t2i_top
     return res
 
 

@@ -326,13 +326,14 @@ class CLIPAdapterTrainer:
                 val_loss += outputs["loss"].item()
         return val_loss / len(self.val_dataloader)
 
-    def evaluate_retrieval(self, ks=(1, 5, 10)):
+    def evaluate_retrieval(self, ks=(1, 5, 10), topk=0):
         """Recall@K and median / mean rank (image->text and text->image) over the whole validation set, on the
         device (clipmi.evaluation.evaluate_retrieval); unlike evaluate()'s mean batch loss it does not depend
-        on the batch size.  No reference counterpart."""
+        on the batch size.  topk > 0 adds the top-k retrieved lists (``i2t_topk`` / ``t2i_topk``).  No reference
+        counterpart."""
         assert self.val_dataloader is not None, "val_dataloader must not be None to run eval"
         from .evaluation import evaluate_retrieval
-        return evaluate_retrieval(self.model, self.val_dataloader, ks=ks)
+        return evaluate_retrieval(self.model, self.val_dataloader, ks=ks, topk=topk)
 
     def save_model(self, path):
         self.model.save_adapter_weights(f"{path}.pt")

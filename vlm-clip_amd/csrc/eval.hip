@@ -222,7 +222,7 @@ __global__ __launch_bounds__(ET) void classify_kernel(const float* probs, const 
   }
 }
 
-bool vec_ok(const float* S, int64_t lds) { return ((uintptr_t)S & 15) == 0 && lds % 4 == 0; }
+}  // namespace
 
 int check_block(const char* who, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols) {
   const std::string f(who);
@@ -234,8 +234,6 @@ int check_block(const char* who, const float* S, int64_t lds, int N, int M, int 
   if (!S) return clipmi_invalid(f + ": null score block");
   return CLIPMI_OK;
 }
-
-}  // namespace
 
 extern "C" int clipmi_rank_pick(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0,
                                 int cols, const int64_t* target, float* target_score, int* bad) {
@@ -254,7 +252,7 @@ extern "C" int clipmi_rank_count(void* stream, const float* S, int64_t lds, int 
   CLIPMI_TRY(check_block(__func__, S, lds, N, M, row0, rows, col0, cols));
   CLIPMI_REQUIRE(target || N == M, "paired targets (target == NULL) need N == M");
   CLIPMI_REQUIRE(target_score && greater && equal && top1 && top1_score, "null input or output");
-  const bool vec = vec_ok(S, lds);
+  const bool vec = block_vec_ok(S, lds);
   const hipStream_t s = (hipStream_t)stream;
   if (cols > WIDE_COLS) {
     auto k = vec ? rank_count_wg_kernel<true> : rank_count_wg_kernel<false>;

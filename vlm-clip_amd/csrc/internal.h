@@ -34,6 +34,13 @@ inline hipError_t lds_optin(const void* fn, int bytes) {
 
 #define CLIPMI_TRY(call) do { int s_ = (call); if (s_ != CLIPMI_OK) return s_; } while (0)
 
+// The score block of the evaluation entry points (eval.hip, topk.hip): rows [row0, row0 + rows) of N queries by
+// columns [col0, col0 + cols) of M candidates, fp32 with row stride lds.  CLIPMI_ERR_INVALID naming `who` on a bad
+// geometry or a null block (eval.hip).
+int check_block(const char* who, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols);
+// whether its rows can be read with 16-byte loads
+inline bool block_vec_ok(const float* S, int64_t lds) { return ((uintptr_t)S & 15) == 0 && lds % 4 == 0; }
+
 
 // ---- live kernel profiler (clipmi_prof_*): while armed for a variant label, launches with
 // that label are bracketed by hipEvents on their own stream, so a caller can time one kernel
