@@ -158,11 +158,16 @@ int clipmi_layernorm_bwd3(void* stream, int x_dtype, int dtype, int w_dtype, con
                           const void* x, int64_t ldx, const float* mean, const float* rstd, const void* w, void* dx,
                           int64_t lddx, const void* dres, int64_t ldres, float* dw, float* db, int beta_wb, void* ws,
                           int64_t ws_bytes, int R, int D);
-/* out[n] (+)= sum_r x[r][n]  (bias gradients of every Linear on the path) */
+/* out[n] (+)= sum_r x[r][n]  (bias gradients of every Linear on the path).  Any N, ldx >= N and alignment: the
+ * 4-column vector kernels run when N % 4 == 0, ldx % 4 == 0, x is aligned to 4 elements (8 bytes bf16, 16 bytes
+ * fp32) and ws to 16 bytes; otherwise the call falls to the one-column-per-thread kernels, which need none of it.
+ * Two fixed-order stages (per-chunk partial rows in ws, then their sum): bitwise reproducible. */
 int64_t clipmi_colsum_ws(int R, int N);
 int clipmi_colsum(void* stream, int dtype, const void* x, int64_t ldx, int R, int N, float* out, int beta, void* ws,
                   int64_t ws_bytes);
-/* out[t][c] (+)= sum_b x[(b*period+t)][c] for t < nt  (position / class embedding gradients) */
+/* out[t][c] (+)= sum_b x[(b*period+t)][c] for t < nt  (position / class embedding gradients); rows t >= nt of out
+ * are not touched.  4-element vector accesses throughout: D % 4 == 0, ldx % 4 == 0, x aligned to 4 elements
+ * (8 bytes bf16, 16 bytes fp32) and out to 16 bytes, else CLIPMI_ERR_INVALID. */
 int clipmi_period_sum(void* stream, int dtype, const void* x, int64_t ldx, int nb, int period, int nt, int D,
                       float* out, int beta);
 
@@ -193,11 +198,17 @@ int clipmi_adapter_bwd(void* stream, int dtype, int R, int D, int A, const void*
 
 /* ---- Embeddings ------------------------------------------------------------------------------
  * text: x0[r] = tok[ids[r]] + pos[r % S]   ([HF] CLIPTextEmbeddings.forward :232-256);
- * *bad_flag |= 1 on an out-of-vocabulary id (Python raises IndexError like nn.Embedding). */
+ * *bad_flag |= 1 on an out-of-vocabulary id (Python raises IndexError like nn.Embedding; the row then reads
+ * tok[0]).  4-element vector accesses: D % 4 == 0 and tok, pos, x0 aligned to 4 elements (8 bytes bf16, 16 bytes
+ * fp32), else CLIPMI_ERR_INVALID.  R = 0 is a no-op. */
 int clipmi_text_embed(void* stream, int dtype, const int64_t* ids, const void* tok, const void* pos, void* x0, int R,
                       int S, int D, int V, int* bad_flag);
 int64_t clipmi_text_embed_bwd_ws(int R, int V);
-/* gtok[v] (+)= sum_{r: ids[r]==v} dx0[r]  (counting sort, one wave per id, no float atomics) */
+/* gtok[v] (+)= sum_{r: ids[r]==v} dx0[r]; rows with an id outside [0, V) contribute nothing.  A counting sort of
+ * the ids, then one wave per 64 rows of the sorted order, which adds its run of each id onto gtok with fp32
+ * atomicAdd whenever the id changes: the sum's order, and so its last bits, may differ between replays (the one
+ * gradient DESIGN.md exempts from bitwise replay).  D % 4 == 0, dx0 aligned to 4 elements; ws need not be
+ * initialised. */
 int clipmi_text_embed_bwd(void* stream, int dtype, const int64_t* ids, const void* dx0, int R, int D, int V,
                           float* gtok, int beta, void* ws, int64_t ws_bytes);
 /* vision: Conv2d(k=s=P, no bias) as im2col + GEMM ([HF] :148-154, :211-212).  X is
@@ -217,7 +228,9 @@ int clipmi_im2col_u8(void* stream, int dtype, const uint8_t* images, void* X, in
 int64_t clipmi_resize_u8_ws(int B, int Hin, int Win, int Hout, int Wout);
 int clipmi_resize_u8(void* stream, const uint8_t* in, int B, int Hin, int Win, uint8_t* out, int Hout, int Wout,
                      void* ws, int64_t ws_bytes);
-/* pooled token per row: mode 0 first token (model_m.py:102), 1 first EOS, 2 argmax id ([HF] :561-581) */
+/* pooled token per row: mode 0 first token (model_m.py:102), 1 first EOS (0 when the row has none), 2 argmax id,
+ * the first of tied maxima ([HF] :561-581).  gather: out[b] = src[b*S + idx[b]]; scatter: dst[b*S + idx[b]] (+)=
+ * src[b], the other rows of dst untouched; idx NULL: token 0.  B = 0 is a no-op. */
 int clipmi_pool_index(void* stream, const int64_t* ids, int B, int S, int64_t eos, int mode, int* idx);
 int clipmi_gather_rows(void* stream, int dtype, const void* src, const int* idx, int B, int S, int D, void* out);
 int clipmi_scatter_rows(void* stream, int dtype, const void* src, const int* idx, int B, int S, int D, void* dst,
@@ -364,7 +377,7 @@ int clipmi_encoder_bwd(void* stream, const clipmi_encoder_desc* d, void* dx);
  * can be all-reduced while the next chunk runs) */
 int clipmi_encoder_bwd_layers(void* stream, const clipmi_encoder_desc* d, void* dx, int layer_hi, int layer_lo);
 
-/* ---- Contrastive head (model_m.py:146-171), fp32 -------------------------------------------- */
+/* ---- Contrastive head (model_m.py:146-171), fp32; every entry point is a no-op at B = 0 ------ */
 int clipmi_l2norm_fwd(void* stream, const float* x, float* y, float* nrm, int B, int E);
 int clipmi_l2norm_bwd(void* stream, const float* dy, const float* y, const float* nrm, float* dx, int B, int E);
 /* logits = exp(*logit_scale) * S over a [B, Bg] cosine block; lse, ce per row (label0 + i) */

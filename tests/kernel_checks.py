@@ -390,3 +390,339 @@ def ln_leading_dims(D, strided):
     if strided == "vec":
         return [D + 4 * k for k in (1, 2, 3, 4, 5)]
     return [D + k for k in (1, 3, 5, 7, 9)]
+
+
+# ------------------------------------------------------------------------------------------------ exact sums
+# The gradient reductions and the row gather / scatter (tests/test_gpu_reductions.py): every summed operand is an
+# integer tensor whose partial and total sums stay below 2^24, so the fp32 result is exact in any order and the
+# reference is an int64 sum.  The functions below restate the host arithmetic of the entry points (csrc/norm.hip,
+# csrc/optim.hip), so that tests/test_cpu_kernel_checks.py can assert the loop regime every case is named for.
+EXACT = 2 ** 24
+
+
+def untouched(view):
+    """True where no byte of a guarded view has been stored to (it still holds the guard pattern)."""
+    return bool((view.contiguous().view(torch.uint8) == GUARD_PATTERN).all())
+
+
+# ---- clipmi_colsum
+COLSUM_LO, COLSUM_HI, BETA_MAX = -3, 8, 4  # x in [-3, 8] (sums grow with R), the accumulated-onto out in [-4, 4]
+
+
+class ColsumCase:
+    """out[N] (+)= column sums of x [R, N] with row stride N + ld_pad, x shifted x_off elements off a 16-byte
+    boundary.  regime: what the case is there for (asserted from colsum_plan on the CPU)."""
+
+    def __init__(self, R, N, ld_pad=0, x_off=0, beta=0, regime="vec"):
+        self.R, self.N, self.ld_pad, self.x_off, self.beta, self.regime = R, N, ld_pad, x_off, beta, regime
+
+    def id(self):
+        return f"R{self.R}-N{self.N}-ld{self.ld_pad}-off{self.x_off}-b{self.beta}-{self.regime}"
+
+
+def colsum_plan(R, N, ldx, x_off):
+    """clipmi_colsum's host arithmetic and the loops of its second stage: chunks = clamp(ceil(R / 256), 1, 512),
+    rows_per = ceil(R / chunks); the vector kernels when N, ldx and x's offset are multiples of 4 elements (8 bytes
+    bf16, 16 bytes fp32; the workspace of the tests is 16-byte aligned), else one column per thread.  unrolled /
+    remainder: whether some partial group of the reducer runs its unrolled loop / the loop after it
+    (reduce_partials4_kernel: 64 groups, 8 partial rows 64 apart per unrolled pass; reduce_partials_kernel: 16
+    groups, 2 rows 16 apart per pass, then at most one more)."""
+    chunks = min(max((R + 255) // 256, 1), 512)
+    rows_per = (R + chunks - 1) // chunks
+    vec = N % 4 == 0 and ldx % 4 == 0 and x_off % 4 == 0
+    groups, depth, step = (64, 8, 64) if vec else (16, 2, 16)
+    unrolled = remainder = False
+    for ty in range(groups):
+        p = ty
+        while p + (depth - 1) * step < chunks:
+            unrolled = True
+            p += depth * step
+        remainder |= p < chunks
+    return dict(chunks=chunks, rows_per=rows_per, vec=vec, unrolled=unrolled, remainder=remainder,
+                col_blocks=((N // 4 if vec else N) + 255) // 256)
+
+
+def colsum_cases():
+    cases = []
+    # the vector kernels at every small R x N x ldx x beta; N = 1028: a second column block with one live thread
+    for R in (1, 255, 257):
+        for N in (4, 8, 1028):
+            for ld_pad in (0, 4):
+                for beta in (0, 1):
+                    cases.append(ColsumCase(R, N, ld_pad, 0, beta, "vec"))
+    # 449 chunks: partial group 0 of reduce_partials4 runs its unrolled loop, the others the remainder loop;
+    # 131,073 rows: the chunk count capped at 512, so rows_per = 257
+    for R, regime in ((114944, "vec-unrolled"), (131073, "vec-capped")):
+        cases.append(ColsumCase(R, 8, 0, 0, 1, regime))
+        cases.append(ColsumCase(R, 8, 4, 0, 0, regime))
+    # one column per thread: N % 4 != 0, ldx % 4 != 0 or x off its vector boundary
+    for R in (1, 255, 257):
+        for i, N in enumerate((1, 5, 257)):
+            cases.append(ColsumCase(R, N, 0, 0, (R + i) % 2, "scalar"))
+            cases.append(ColsumCase(R, N, 1, 0, (R + i + 1) % 2, "scalar"))
+        cases.append(ColsumCase(R, 8, 1, 0, R % 2, "scalar"))       # N % 4 == 0, ldx = N + 1
+        cases.append(ColsumCase(R, 8, 4, 1, (R + 1) % 2, "scalar"))  # N, ldx % 4 == 0, x one element off
+    cases.append(ColsumCase(114944, 5, 1, 0, 1, "scalar-unrolled"))
+    cases.append(ColsumCase(131073, 1, 0, 0, 0, "scalar-capped"))
+    cases.append(ColsumCase(131073, 8, 4, 1, 1, "scalar-capped"))
+    ids = [c.id() for c in cases]
+    assert len(set(ids)) == len(ids), "duplicate colsum case"
+    return cases
+
+
+def colsum_inputs(case, dtype):
+    """(x [R, N] of dtype on the CPU, out0 [N] fp32, ref [N] int64): the same integers for both dtypes."""
+    x = integer_tensor((case.R, case.N), COLSUM_LO, COLSUM_HI, dtype, 17 + case.R + case.N)
+    out0 = integer_tensor((case.N,), -BETA_MAX, BETA_MAX, torch.float32, 18 + case.N)
+    ref = x.long().sum(0) + (out0.long() if case.beta else 0)
+    return x, out0, ref
+
+
+# ---- clipmi_period_sum
+PERIOD_NB = [1, 4, 5, 28, 29, 32, 33, 61]
+PERIOD_PT = [(1, 1), (50, 50), (50, 1), (50, 7)]
+PERIOD_D = [4, 252, 256, 260, 768]
+PERIOD_MAX = 8  # x in [-8, 8]
+
+
+class PeriodCase:
+    """out[t][:] (+)= sum over b < nb of x[b * period + t][:] for t < nt; x [nb * period, D], row stride D + ld_pad."""
+
+    def __init__(self, nb, period, nt, D, ld_pad, beta):
+        self.nb, self.period, self.nt, self.D, self.ld_pad, self.beta = nb, period, nt, D, ld_pad, beta
+
+    def id(self):
+        return f"nb{self.nb}-p{self.period}-nt{self.nt}-D{self.D}-ld{self.ld_pad}-b{self.beta}"
+
+
+def period_plan(nb):
+    """period_sum_kernel's loops: wave w of 4 takes rows b = w, w + 4, ...; the 8-deep unrolled loop runs while
+    b + 28 < nb (b += 32), the tail loop takes what is left.  Returns per wave (unrolled passes, tail rows)."""
+    plan = []
+    for w in range(4):
+        b, passes, tail = w, 0, 0
+        while b + 28 < nb:
+            passes += 1
+            b += 32
+        while b < nb:
+            tail += 1
+            b += 4
+        plan.append((passes, tail))
+    return plan
+
+
+def period_cases():
+    cases = []
+    for i, nb in enumerate(PERIOD_NB):  # every nb with (50, 7) and D = 260, ldx and beta alternating
+        cases.append(PeriodCase(nb, 50, 7, 260, 4 * (i % 2), (i // 2) % 2))
+        cases.append(PeriodCase(nb, 50, 7, 260, 4 * ((i + 1) % 2), (i // 2 + 1) % 2))
+    # the other (period, nt) and widths, in and out of the unrolled loop
+    cases += [PeriodCase(61, 1, 1, 4, 0, 0), PeriodCase(5, 1, 1, 768, 4, 1), PeriodCase(33, 50, 50, 252, 4, 1),
+              PeriodCase(4, 50, 50, 256, 0, 0), PeriodCase(29, 50, 1, 768, 0, 1), PeriodCase(28, 50, 1, 4, 4, 0),
+              PeriodCase(32, 50, 7, 256, 4, 0), PeriodCase(61, 50, 7, 252, 0, 1), PeriodCase(1, 50, 50, 768, 4, 0)]
+    ids = [c.id() for c in cases]
+    assert len(set(ids)) == len(ids), "duplicate period_sum case"
+    return cases
+
+
+def period_inputs(case, dtype):
+    """(x [nb * period, D] on the CPU, out0 [nt, D] fp32, ref [nt, D] int64)."""
+    c = case
+    x = integer_tensor((c.nb * c.period, c.D), -PERIOD_MAX, PERIOD_MAX, dtype, 31 + c.nb + c.D + c.period)
+    out0 = integer_tensor((c.nt, c.D), -BETA_MAX, BETA_MAX, torch.float32, 32 + c.D)
+    ref = x.long().view(c.nb, c.period, c.D)[:, :c.nt].sum(0) + (out0.long() if c.beta else 0)
+    return x, out0, ref
+
+
+# ---- clipmi_text_embed_bwd / clipmi_text_embed
+EMBED_PATTERNS = ["equal", "distinct", "ascending", "alternate", "eos_tail", "oov"]
+EMBED_V = [1, 1000, 1024, 1025, 49408]
+EMBED_R = [1, 63, 64, 65, 257, 5000]
+EMBED_D = [4, 260, 512]
+EMBED_MAX = 3       # dx0 in [-3, 3]
+EMBED_OOV = [-1, None, 2 ** 40]  # None: V itself
+
+
+class EmbedBwdCase:
+    def __init__(self, V, R, D, pattern, beta):
+        self.V, self.R, self.D, self.pattern, self.beta = V, R, D, pattern, beta
+
+    def id(self):
+        return f"V{self.V}-R{self.R}-D{self.D}-{self.pattern}-b{self.beta}"
+
+
+def embed_bwd_cases():
+    rows = [(1, 1, 4, "equal", 0), (1, 5000, 260, "equal", 1), (1, 64, 512, "oov", 0),
+            (1000, 63, 512, "distinct", 0), (1000, 64, 260, "alternate", 1), (1000, 65, 4, "ascending", 0),
+            (1000, 5000, 260, "eos_tail", 1), (1000, 257, 512, "oov", 0), (1000, 5000, 4, "equal", 0),
+            (1024, 257, 260, "distinct", 1), (1024, 5000, 4, "oov", 1), (1024, 64, 512, "ascending", 1),
+            (1025, 65, 260, "distinct", 0), (1025, 5000, 260, "eos_tail", 0), (1025, 257, 512, "alternate", 0),
+            (1025, 1, 4, "equal", 1),
+            (49408, 5000, 4, "eos_tail", 1), (49408, 5000, 4, "oov", 0), (49408, 5000, 4, "distinct", 0),
+            (49408, 64, 4, "ascending", 1), (49408, 1, 4, "equal", 0), (49408, 5000, 4, "equal", 1),
+            (49408, 63, 4, "alternate", 0), (49408, 257, 4, "ascending", 0)]
+    return [EmbedBwdCase(*r) for r in rows]
+
+
+def scan_per(V):
+    """id_scan_kernel: the vocabulary entries each of its 1024 threads scans."""
+    return (V + 1023) // 1024
+
+
+def embed_ids(V, R, pattern, seed):
+    """int64 [R] ids of a pattern; the last id of the vocabulary is used wherever a pattern names one id."""
+    g = torch.Generator().manual_seed(seed)
+    rand = torch.randint(0, V, (R,), generator=g)
+    if pattern == "equal":        # one id owns every 64-row chunk
+        return torch.full((R,), V - 1, dtype=torch.int64)
+    if pattern == "distinct":     # R <= V: every chunk flushes at every row
+        assert R <= V
+        return torch.randperm(V, generator=g)[:R].contiguous()
+    if pattern == "ascending":
+        return rand.sort().values
+    if pattern == "alternate":
+        return torch.where(torch.arange(R) % 2 == 0, V - 1, V // 2).to(torch.int64)
+    if pattern == "eos_tail":     # the last 40 % of the rows hold the last id, like EOS padding
+        rand[R - (2 * R) // 5:] = V - 1
+        return rand
+    assert pattern == "oov"       # about a third of the rows: -1, V and 2^40 in turn
+    bad = torch.rand(R, generator=g) < 0.34
+    if R >= 3:
+        bad[:3] = True
+    oov = torch.tensor([V if v is None else v for v in EMBED_OOV], dtype=torch.int64)
+    return torch.where(bad, oov[torch.arange(R) % 3], rand)
+
+
+def embed_bwd_inputs(case, dtype):
+    """(ids [R] int64, dx0 [R, D] of dtype, g0 [V, D] fp32, ref1, ref2 [V, D] int64): ref1 after one call, ref2
+    after a second one on the same buffers (beta: g0 + 2 sums; else the sum again)."""
+    c = case
+    ids = embed_ids(c.V, c.R, c.pattern, 41 + c.V + c.R)
+    dx0 = integer_tensor((c.R, c.D), -EMBED_MAX, EMBED_MAX, dtype, 42 + c.R + c.D)
+    g0 = integer_tensor((c.V, c.D), -BETA_MAX, BETA_MAX, torch.float32, 43 + c.V)
+    ok = (ids >= 0) & (ids < c.V)
+    s = torch.zeros(c.V, c.D, dtype=torch.int64).index_add_(0, ids[ok], dx0.long()[ok])
+    if c.beta:
+        return ids, dx0, g0, g0.long() + s, g0.long() + 2 * s
+    return ids, dx0, g0, s, s
+
+
+# (B, S, D, V): R = B * S is no multiple of 4; S in {1, 77}; every D
+EMBED_FWD_CASES = [(3, 77, 260, 1000), (5, 1, 4, 2), (1, 77, 512, 1025), (7, 1, 512, 1000), (3, 77, 4, 49408),
+                   (9, 1, 260, 1)]
+
+
+def embed_fwd_ids(B, S, V, seed):
+    """Random valid ids [B * S] with 0 and V - 1 present."""
+    ids = torch.randint(0, V, (B * S,), generator=torch.Generator().manual_seed(seed))
+    ids[0], ids[-1] = V - 1, 0
+    if B * S > 2:
+        ids[1] = 0
+    return ids
+
+
+# ---- clipmi_pool_index / clipmi_gather_rows / clipmi_scatter_rows
+ROWS_B = [1, 255, 256, 257]
+ROWS_S = [1, 77]
+ROWS_D = [1, 255, 256, 257, 768]
+POOL_KINDS = ["first_token", "no_eos", "several_eos", "tied_max"]
+POOL_EOS = 49407
+
+
+def pool_inputs(kind, B, S, seed):
+    """(ids [B, S] int64, mode, expected [B] int32)."""
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(0, 1000, (B, S), generator=g)
+    pos = torch.arange(S).expand(B, S)
+    if kind == "first_token":
+        ids[:, S // 2] = POOL_EOS
+        return ids, 0, torch.zeros(B, dtype=torch.int32)
+    if kind == "no_eos":
+        return ids, 1, torch.zeros(B, dtype=torch.int32)
+    hit = torch.rand(B, S, generator=g) < 0.2  # several positions per row; at least the row's own, (b + S // 2) mod S
+    hit[torch.arange(B), (torch.arange(B) + S // 2) % S] = True
+    if kind == "several_eos":
+        ids[hit] = POOL_EOS
+        mode = 1
+    else:  # the maximum at several positions, below it everywhere else
+        ids[hit] = 1000 + (torch.arange(B)[:, None].expand(B, S))[hit]
+        mode = 2
+    first = torch.where(hit, pos, torch.full_like(pos, S)).min(1).values
+    return ids, mode, first.to(torch.int32)
+
+
+def rows_cases():
+    """(B, S, D): every B with every D at S = 1; every D at S = 77 with one row; every B at S = 77 with D = 1."""
+    cases = [(B, 1, D) for B in ROWS_B for D in ROWS_D]
+    cases += [(1, 77, D) for D in ROWS_D if (1, 77, D) not in cases]
+    cases += [(B, 77, 1) for B in ROWS_B if (B, 77, 1) not in cases]
+    cases.append((5, 77, 257))
+    return cases
+
+
+def rows_idx(B, S, seed):
+    """int32 [B] token positions with 0 and S - 1 present."""
+    idx = torch.randint(0, S, (B,), generator=torch.Generator().manual_seed(seed)).to(torch.int32)
+    idx[0] = S - 1
+    idx[-1] = 0 if B > 1 else S - 1
+    return idx
+
+
+# ---- clipmi_grad_norm / _multi / clipmi_grad_scale / clipmi_sum2
+NORM_PASS = 1024 * 256 * 4  # elements of one grid-stride pass of sumsq_partial_kernel: 1024 blocks x 256 lanes x 4
+GRAD_NS = [1, 3, 4, 5, 1023, NORM_PASS + 7]
+GRAD_MULTI_NS = [5, NORM_PASS + 7, 0]
+GRAD_MAX = 3
+SUM2_NS = [1, 1023, 1025, 5000]
+
+
+def grad_plan(n):
+    """sumsq_partial_kernel over n elements: (full grid-stride passes of the vector loop, vectors of a further
+    partial pass, scalar tail elements)."""
+    n4 = n // 4
+    return n4 // (NORM_PASS // 4), n4 % (NORM_PASS // 4), n - 4 * n4
+
+
+def grad_tensor(n, seed):
+    """Integers in [-3, 3], fp32 [n], first and last element non-zero."""
+    g = integer_tensor((n,), -GRAD_MAX, GRAD_MAX, torch.float32, seed)
+    g[0], g[-1] = -3.0, 3.0
+    return g
+
+
+def clip_expect(sumsq, max_norm):
+    """(norm as fp32, the clip coefficient: exactly 1.0 where the contract says so, else the fp64 value of
+    max_norm / (norm + 1e-6) on the fp32 norm, fp32 constant and fp32 max_norm)."""
+    norm = torch.tensor(float(sumsq), dtype=torch.float64).sqrt().float()
+    mn = float(torch.tensor(max_norm, dtype=torch.float32))
+    if mn <= 0 or float(norm) == 0.0 or float(norm) < mn:
+        return norm, 1.0
+    eps = float(torch.tensor(1e-6, dtype=torch.float32))
+    return norm, min(1.0, mn / (float(norm) + eps))
+
+
+# ---- clipmi_l2norm_* / clipmi_softmax_rows*
+L2_ES = [1, 4, 63, 64, 65, 512, 1000]
+L2_BS = [1, 4, 5]
+SM_NS = [1, 63, 64, 65, 200]
+SM_RS = [1, 4, 5]
+
+
+def l2norm_rows(B, E, entries, seed):
+    """x [B, E] fp32 with `entries` (1 or 4) non-zero elements +-2^k per row, k in [-3, 3] by row: |x| = 2^k or
+    2^(k+1), so y = +-1 or +-0.5 exactly.  Returns (x, y, nrm)."""
+    assert entries in (1, 4) and E >= entries
+    g = torch.Generator().manual_seed(seed)
+    x = torch.zeros(B, E)
+    y = torch.zeros(B, E)
+    nrm = torch.zeros(B)
+    for r in range(B):
+        k = r % 7 - 3
+        cols = torch.randperm(E, generator=g)[:entries]
+        if r == 0 and E - 1 not in cols.tolist():
+            cols[0] = E - 1  # row 0: the row's last element is live
+        sign = (torch.randint(0, 2, (entries,), generator=g) * 2 - 1).float()
+        x[r, cols] = sign * 2.0 ** k
+        y[r, cols] = sign * (1.0 if entries == 1 else 0.5)
+        nrm[r] = 2.0 ** (k if entries == 1 else k + 1)
+    return x, y, nrm

@@ -182,6 +182,7 @@ __global__ __launch_bounds__(1024) void sum2_kernel(const float* a, const float*
 }  // namespace
 
 extern "C" int clipmi_l2norm_fwd(void* stream, const float* x, float* y, float* nrm, int B, int E) {
+  if (B == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(l2norm_fwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, y, nrm, B, E);
   CLIPMI_CHECK_LAUNCH();
   return CLIPMI_OK;
@@ -189,6 +190,7 @@ extern "C" int clipmi_l2norm_fwd(void* stream, const float* x, float* y, float* 
 
 extern "C" int clipmi_l2norm_bwd(void* stream, const float* dy, const float* y, const float* nrm, float* dx, int B,
                                  int E) {
+  if (B == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, y, nrm, dx, B, E);
   CLIPMI_CHECK_LAUNCH();
   return CLIPMI_OK;
@@ -197,6 +199,7 @@ extern "C" int clipmi_l2norm_bwd(void* stream, const float* dy, const float* y, 
 extern "C" int clipmi_contrastive_ce_fwd(void* stream, const float* S, float* logits, const float* logit_scale, int B,
                                          int Bg, int label0, float* lse, float* ce) {
   CLIPMI_REQUIRE(label0 >= 0 && label0 + B <= Bg, "label offset out of range");
+  if (B == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(ce_fwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, logits, logit_scale, B, Bg,
                      label0, lse, ce);
   CLIPMI_CHECK_LAUNCH();
@@ -207,6 +210,7 @@ extern "C" int clipmi_contrastive_ce_bwd(void* stream, const float* logits, cons
                                          const float* grad_out, int B, int Bg, int label0, float norm, float* dS,
                                          float* dls_row) {
   CLIPMI_REQUIRE(label0 >= 0 && label0 + B <= Bg, "label offset out of range");
+  if (B == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, lse, logit_scale,
                      grad_out, B, Bg, label0, norm, dS, dls_row);
   CLIPMI_CHECK_LAUNCH();
@@ -217,6 +221,7 @@ extern "C" int clipmi_contrastive_ce_fwd_chunk(void* stream, const float* S, con
                                                int col0, int Bg, int label0, float* run, float* lab) {
   CLIPMI_REQUIRE(label0 >= 0 && label0 + B <= Bg, "label offset out of range");
   CLIPMI_REQUIRE(C > 0 && col0 >= 0 && col0 + C <= Bg, "chunk out of range");
+  if (B == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(ce_fwd_chunk_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, logit_scale, B, C,
                      col0, label0, run, lab);
   CLIPMI_CHECK_LAUNCH();
@@ -225,6 +230,7 @@ extern "C" int clipmi_contrastive_ce_fwd_chunk(void* stream, const float* S, con
 
 extern "C" int clipmi_contrastive_ce_finish(void* stream, const float* run, const float* lab, int B, float* lse,
                                             float* ce) {
+  if (B == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(ce_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, run, lab, B, lse, ce);
   CLIPMI_CHECK_LAUNCH();
   return CLIPMI_OK;
@@ -235,6 +241,7 @@ extern "C" int clipmi_contrastive_ce_bwd_chunk(void* stream, const float* S, con
                                                float norm, float* dS, float* dls_row, int beta) {
   CLIPMI_REQUIRE(label0 >= 0 && label0 + B <= Bg, "label offset out of range");
   CLIPMI_REQUIRE(C > 0 && col0 >= 0 && col0 + C <= Bg, "chunk out of range");
+  if (B == 0) return CLIPMI_OK;
   hipLaunchKernelGGL(ce_bwd_chunk_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lse, logit_scale,
                      grad_out, B, C, col0, label0, norm, dS, dls_row, beta);
   CLIPMI_CHECK_LAUNCH();

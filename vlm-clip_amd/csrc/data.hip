@@ -339,12 +339,14 @@ extern "C" int clipmi_im2col_u8(void* stream, int dtype, const uint8_t* images, 
 }
 
 extern "C" int clipmi_pool_index(void* stream, const int64_t* ids, int B, int S, int64_t eos, int mode, int* idx) {
+  if (B == 0) return CLIPMI_OK;  // no row: nothing to launch (a grid of 0 blocks is an invalid configuration)
   hipLaunchKernelGGL(pool_index_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, ids, B, S, eos, mode, idx);
   CLIPMI_CHECK_LAUNCH();
   return CLIPMI_OK;
 }
 
 extern "C" int clipmi_gather_rows(void* stream, int dtype, const void* src, const int* idx, int B, int S, int D, void* out) {
+  if (B == 0) return CLIPMI_OK;
   if (dtype == CLIPMI_BF16) hipLaunchKernelGGL(gather_rows_kernel<bf16>, dim3(B), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, idx, B, S, D, (bf16*)out);
   else hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)stream, (const float*)src, idx, B, S, D, (float*)out);
   CLIPMI_CHECK_LAUNCH();
@@ -352,6 +354,7 @@ extern "C" int clipmi_gather_rows(void* stream, int dtype, const void* src, cons
 }
 
 extern "C" int clipmi_scatter_rows(void* stream, int dtype, const void* src, const int* idx, int B, int S, int D, void* dst, int beta) {
+  if (B == 0) return CLIPMI_OK;
   if (dtype == CLIPMI_BF16) hipLaunchKernelGGL(scatter_rows_kernel<bf16>, dim3(B), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, idx, B, S, D, (bf16*)dst, beta);
   else hipLaunchKernelGGL(scatter_rows_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)stream, (const float*)src, idx, B, S, D, (float*)dst, beta);
   CLIPMI_CHECK_LAUNCH();

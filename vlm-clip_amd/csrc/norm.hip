@@ -1022,7 +1022,9 @@ extern "C" int clipmi_colsum(void* stream, int dtype, const void* x, int64_t ldx
   if (N == 0) return CLIPMI_OK;
   int rows_per = (R + chunks - 1) / chunks;
   const size_t al = dtype == CLIPMI_BF16 ? 8 : 16;  // load4's vector width
-  if (N % 4 || ldx % 4 || ((uintptr_t)x & (al - 1))) {
+  // the vector kernels move 4 columns at once: x rows as load4, the partial rows of ws as 16-byte stores and loads
+  // (N % 4 == 0 keeps every partial row of a 16-byte aligned ws aligned); anything else takes one column per thread
+  if (N % 4 || ldx % 4 || ((uintptr_t)x & (al - 1)) || ((uintptr_t)ws & 15)) {
     dim3 g1((N + 255) / 256, chunks);
     if (dtype == CLIPMI_BF16) hipLaunchKernelGGL(colsum_partial1_kernel<bf16>, g1, dim3(256), 0, s, (const bf16*)x, ldx, R, N, rows_per, (float*)ws);
     else hipLaunchKernelGGL(colsum_partial1_kernel<float>, g1, dim3(256), 0, s, (const float*)x, ldx, R, N, rows_per, (float*)ws);
@@ -1033,10 +1035,7 @@ extern "C" int clipmi_colsum(void* stream, int dtype, const void* x, int64_t ldx
   dim3 g((N / 4 + 255) / 256, chunks);
   if (dtype == CLIPMI_BF16) hipLaunchKernelGGL(colsum_partial_kernel<bf16>, g, dim3(256), 0, s, (const bf16*)x, ldx, R, N, rows_per, (float*)ws);
   else hipLaunchKernelGGL(colsum_partial_kernel<float>, g, dim3(256), 0, s, (const float*)x, ldx, R, N, rows_per, (float*)ws);
-  if (((uintptr_t)ws & 15) == 0 && N % 4 == 0)
-    hipLaunchKernelGGL(reduce_partials4_kernel, dim3((N + 63) / 64), dim3(1024), 0, s, (const float*)ws, (int64_t)N, chunks, N, out, (float*)nullptr, beta);
-  else
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((N + 63) / 64), dim3(1024), 0, s, (const float*)ws, (int64_t)N, chunks, N, out, beta);
+  hipLaunchKernelGGL(reduce_partials4_kernel, dim3((N + 63) / 64), dim3(1024), 0, s, (const float*)ws, (int64_t)N, chunks, N, out, (float*)nullptr, beta);
   CLIPMI_CHECK_LAUNCH();
   return CLIPMI_OK;
 }
@@ -1046,6 +1045,10 @@ extern "C" int clipmi_period_sum(void* stream, int dtype, const void* x, int64_t
   hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(D % 4 == 0, "D % 4");
   CLIPMI_REQUIRE(nt >= 1 && nt <= period, "nt must be in [1, period]");
+  const size_t al = dtype == CLIPMI_BF16 ? 8 : 16;  // load4's vector width
+  CLIPMI_REQUIRE(ldx % 4 == 0 && ((uintptr_t)x & (al - 1)) == 0 && ((uintptr_t)out & 15) == 0,
+                 "ldx % 4, x aligned to 4 elements, out 16-byte aligned");
+  if (D == 0) return CLIPMI_OK;
   dim3 g((D / 4 + 63) / 64, nt);
   if (dtype == CLIPMI_BF16) hipLaunchKernelGGL(period_sum_kernel<bf16>, g, dim3(256), 0, s, (const bf16*)x, ldx, nb, period, D, out, beta);
   else hipLaunchKernelGGL(period_sum_kernel<float>, g, dim3(256), 0, s, (const float*)x, ldx, nb, period, D, out, beta);
@@ -1057,6 +1060,9 @@ extern "C" int clipmi_text_embed(void* stream, int dtype, const int64_t* ids, co
                                  void* x0, int R, int S, int D, int V, int* bad_flag) {
   hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(D % 4 == 0, "D % 4");
+  const size_t al = dtype == CLIPMI_BF16 ? 8 : 16;  // load4's / store4's vector width
+  CLIPMI_REQUIRE((((uintptr_t)tok | (uintptr_t)pos | (uintptr_t)x0) & (al - 1)) == 0, "tok, pos, x0 aligned to 4 elements");
+  if (R == 0) return CLIPMI_OK;
   if (dtype == CLIPMI_BF16) hipLaunchKernelGGL(text_embed_kernel<bf16>, dim3((R + 3) / 4), dim3(256), 0, s, ids, (const bf16*)tok, (const bf16*)pos, (bf16*)x0, R, S, D, V, bad_flag);
   else hipLaunchKernelGGL(text_embed_kernel<float>, dim3((R + 3) / 4), dim3(256), 0, s, ids, (const float*)tok, (const float*)pos, (float*)x0, R, S, D, V, bad_flag);
   CLIPMI_CHECK_LAUNCH();
@@ -1071,12 +1077,15 @@ extern "C" int clipmi_text_embed_bwd(void* stream, int dtype, const int64_t* ids
   hipStream_t s = (hipStream_t)stream;
   CLIPMI_REQUIRE(ws_bytes >= clipmi_text_embed_bwd_ws(R, V), "text_embed_bwd workspace too small");
   CLIPMI_REQUIRE(D % 4 == 0, "D % 4");
+  CLIPMI_REQUIRE(((uintptr_t)dx0 & (dtype == CLIPMI_BF16 ? 7 : 15)) == 0 && ((uintptr_t)ws & 3) == 0,
+                 "dx0 aligned to 4 elements, ws to 4 bytes");
   int* counts = (int*)ws;
   int* offs = counts + V;
   int* cursor = offs + V + 1;
   int* perm = cursor + V;
   int* sid = perm + R;
-  if (!beta) CLIPMI_HIP(hipMemsetAsync(gtok, 0, (size_t)V * D * 4, s));
+  if (!beta && V > 0 && D > 0) CLIPMI_HIP(hipMemsetAsync(gtok, 0, (size_t)V * D * 4, s));
+  if (R == 0 || V == 0 || D == 0) return CLIPMI_OK;  // no row to add: gtok is what beta left of it
   CLIPMI_HIP(hipMemsetAsync(counts, 0, (size_t)V * 4, s));
   CLIPMI_HIP(hipMemsetAsync(sid, 0xff, (size_t)R * 4, s));
   hipLaunchKernelGGL(id_count_kernel, dim3((R + 255) / 256), dim3(256), 0, s, ids, R, V, counts);
