@@ -33,7 +33,8 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
 
 /* 2: clipmi_encoder_desc gained first_token (appended); clipmi_encoder_act_bytes
  * 3: evaluation entry points (clipmi_rank_pick, clipmi_rank_count, clipmi_classify_accumulate)
- * 4: clipmi_topk_merge */
+ * 4: clipmi_topk_merge
+ * 5: clipmi_encoder_desc gained cls_last (appended); clipmi_attention_cls_fwd / _bwd, clipmi_layernorm_bwd4 */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -158,6 +159,14 @@ int clipmi_layernorm_bwd3(void* stream, int x_dtype, int dtype, int w_dtype, con
                           const void* x, int64_t ldx, const float* mean, const float* rstd, const void* w, void* dx,
                           int64_t lddx, const void* dres, int64_t ldres, float* dw, float* db, int beta_wb, void* ws,
                           int64_t ws_bytes, int R, int D);
+/* the same with a compact residual gradient (clipmi_version() >= 5): res_period > 0 makes dres
+   [ceil(R / res_period)][ldres], its row b added to row b * res_period alone and nothing to the other rows (the
+   encoder's cls_last layer, whose residual gradient exists at the CLS rows only); res_period == 0 is
+   clipmi_layernorm_bwd3.  One rounding of dx either way. */
+int clipmi_layernorm_bwd4(void* stream, int x_dtype, int dtype, int w_dtype, const void* dy, int64_t lddy,
+                          const void* x, int64_t ldx, const float* mean, const float* rstd, const void* w, void* dx,
+                          int64_t lddx, const void* dres, int64_t ldres, int res_period, float* dw, float* db,
+                          int beta_wb, void* ws, int64_t ws_bytes, int R, int D);
 /* out[n] (+)= sum_r x[r][n]  (bias gradients of every Linear on the path).  Any N, ldx >= N and alignment: the
  * 4-column vector kernels run when N % 4 == 0, ldx % 4 == 0, x is aligned to 4 elements (8 bytes bf16, 16 bytes
  * fp32) and ws to 16 bytes; otherwise the call falls to the one-column-per-thread kernels, which need none of it.
@@ -249,6 +258,23 @@ int clipmi_attention_fwd_mxfp8(void* stream, const void* qkv, uint8_t* o8, uint8
                                const int64_t* attention_mask, int causal, int B, int H, int N, int D);
 int clipmi_attention_bwd(void* stream, int dtype, const void* qkv, const void* o, const float* lse, const void* dout,
                          void* dqkv, const int64_t* attention_mask, int causal, int B, int H, int N, int D);
+/* Single-query attention (csrc/attention_cls.hip; clipmi_version() >= 5): one query per (sequence, head) -- the
+ * CLS row of the vision tower's last layer -- against all N keys / values.  For hosts that pool one row (inference
+ * or their own training loop); the encoder engine does not call it: its cls_last mode keeps the MFMA attention
+ * kernels so that a step computes the bits of the full mode, and these kernels keep the probabilities in fp32 where
+ * those round them to bf16.  Head dim 64 (D == 64 H), 1 <= N <= 4096,
+ * no mask, dtype bf16 or fp32.  q [B][ldq], kv [B*N][2D] (K | V, head h at h*64 in each half), o [B][ldo],
+ * lse [B][H] fp32.  Per (b, h), scale = 1/8: s_j = scale q.k_j, p = softmax(s), o = sum_j p_j v_j,
+ * lse = log sum_j e^{s_j}.  Backward (p recomputed from lse): dkv [B*N][2D] (dK | dV), dq [B][lddq]; dkv0 (may be
+ * NULL) [B][ld0] receives a second copy of row 0's dK | dV at columns [0, 2D), so a caller can lay
+ * dq | dK_0 | dV_0 out as one [B][3D] operand.  Scores, probabilities and sums are fp32, each output is rounded
+ * once; fixed-order sums, so a replay is bitwise equal.  Pointers 16-byte aligned, leading dimensions multiples of
+ * 16 bytes.  Arguments are checked before any HIP call; B = 0 is a no-op. */
+int clipmi_attention_cls_fwd(void* stream, int dtype, const void* q, int64_t ldq, const void* kv, void* o, int64_t ldo,
+                             float* lse, int B, int H, int N, int D);
+int clipmi_attention_cls_bwd(void* stream, int dtype, const void* q, int64_t ldq, const void* kv, const void* o,
+                             int64_t ldo, const float* lse, const void* dout, int64_t lddo, void* dkv, void* dq,
+                             int64_t lddq, void* dkv0, int64_t ld0, int B, int H, int N, int D);
 /* bf16x3 split images (the layout of CLIPMI_GEMM_SPLIT3's operands): clipmi_split3 writes the image of an fp32
    operand -- k-major X [rows][K] -> bf16 [rows][3K], else X [K][rows] -> [3K][round8(rows)] -- with segments
    (h, h, l) for pattern 0 or (h, l, h) for pattern 1, h = bf16(x), l = bf16(x - h); clipmi_split3_elems gives its
@@ -361,9 +387,27 @@ typedef struct clipmi_encoder_desc {
    * the V weight / bias gradients into grads[l].qkv_w + 2D*D / grads[l].qkv_b + 2D; the q and k slots of both
    * are NOT touched (gradients accumulate, and their exact value is zero).  Not with CLIPMI_FP8 or gemm_x3. */
   int first_token;
+  /* clipmi_version() >= 5: the caller reads row 0 (CLS) of each sequence's output and nothing else (model_m.py:122,
+   * no post-LayerNorm: quirk Q2).  Layers 0 .. L-2 run as usual; in layer L-1 the other rows matter only as keys and
+   * values for the CLS query, so it runs LN1, the q | k | v projection and the attention on all R = B*N rows, with
+   * the full mode's kernels (the CLS row of the attention output keeps the full mode's bits), and everything after
+   * the attention -- out-projection + residual, LN2, fc1, fc2 -- on the B CLS rows (rows b*N, read in place with a
+   * leading dimension of N*D).  x_out is compact [B][D].
+   * Not with causal (such towers use first_token), first_token, CLIPMI_FP8, gemm_x3 or an attention_mask; N <= 4096.
+   * act[L-1] keeps the sizes clipmi_encoder_act_bytes gives for the full mode (cls_last does not change them):
+   *   x_in, ln1, mean1, rstd1, qkv, o, lse   all R rows, as in the full mode
+   *   h, ln2, pre, act, mean2, rstd2         the first B rows
+   * Backward: the dx buffer always holds R*D elements; when the call's layer range includes layer L-1
+   * (layer_hi == L) its first B rows hold dL/dx_out on entry; on exit it holds the [R][D] gradient of
+   * act[layer_lo].x_in as in the full mode.  The MLP's and the out-projection's gradients run on B rows; the attention
+   * backward, the qkv weight gradient and d_ln1 run on all rows with d_o zero outside the CLS rows (the values the
+   * full mode computes there), and LN1's backward adds the compact residual gradient at the CLS rows
+   * (clipmi_layernorm_bwd4).  Activations and activation gradients are bitwise those of the full mode given a
+   * gradient that is zero outside the CLS rows; weight gradients differ by the order of their fp32 sums. */
+  int cls_last;
 } clipmi_encoder_desc;
 /* Bytes of each clipmi_layer_act member for one layer in the descriptor's mode (dtype, resid_f32, gemm_x3,
- * first_token; B, N, D, F, H), in member order: x_in, ln1, qkv, o, h, ln2, pre, act, mean1, rstd1, lse, mean2,
+ * first_token; B, N, D, F, H; cls_last does not change them), in member order: x_in, ln1, qkv, o, h, ln2, pre, act, mean1, rstd1, lse, mean2,
  * rstd2.  0: the member is not used in this mode (may be NULL); pre is needed by a training forward only.
  * Only the shape / mode fields of d are read. */
 int clipmi_encoder_act_bytes(const clipmi_encoder_desc* d, int64_t out[13]);

@@ -12,6 +12,7 @@ main = next(r["Stream_Id"] for r in rows if re.search(r"attn_fwd_(pf|x3)(<|ILi)1
 FAM = [("gemm fwd/dgrad 8-wave", r"gemm_pp_kernel"), ("gemm 4-wave persistent (fwd/dgrad)", r"gemm_w4p_kernel(ILb1|<true)"),
        ("gemm 4-wave persistent (wgrad)", r"gemm_w4p_kernel(ILb0|<false)"), ("gemm wgrad 8-wave", r"gemm256_kernel"),
        ("split-K reduce", r"splitk_reduce"), ("bf16x3 split", r"split3"), ("attention fwd", r"attn_fwd"), ("attention bwd", r"attn_bwd"),
+       ("attention cls fwd (single query)", r"attn_cls_fwd"), ("attention cls bwd (single query)", r"attn_cls_bwd"),
        ("layernorm fwd", r"ln_fwd"), ("layernorm bwd", r"ln_bwd"), ("LN affine-grad reduce", r"reduce_partials"),
        ("adamw / norm", r"adamw|sumsq|grad_norm"), ("embeddings / im2col / pooling", r"im2col|text_embed|id_|period_sum|pool|scatter|gather"),
        ("contrastive", r"ce_|l2norm|gemm_f32|sum2"), ("torch / copies", r"at::native|rocclr")]

@@ -275,7 +275,10 @@ class CLIPWithAdapters(nn.Module):
     def get_image_features(self, pixel_values):
         """model_m.py:107-125: vision tower (no post-LN, quirk Q2) -> adapter -> CLS -> visual_projection."""
         self._rt.train_tower = self._tower_training()
-        h = T.VisionTowerFn.apply(self._check_device(pixel_values), _anchor(self.clip), self._rt)
+        # only the CLS row is read and there is no post-LayerNorm (model_m.py:116-122): the last encoder layer's
+        # out-projection and MLP run for that row alone ([B, 1, D]; the same bits), training or not
+        fn = T.VisionClsFn if T.vision_cls_last(self._rt) else T.VisionTowerFn
+        h = fn.apply(self._check_device(pixel_values), _anchor(self.clip), self._rt)
         if self.use_vision_adapter:  # CLS row only (model_m.py:122), as in get_text_features
             h = T.PoolRowsFn.apply(h, self._rt, None)
             h = T.AdapterFn.apply(h, _anchor(self.vision_adapter), self._rt, self.vision_adapter,

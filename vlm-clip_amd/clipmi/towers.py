@@ -9,6 +9,7 @@ autograd only carries activation gradients between the Functions.
 Reference mapping:
   VisionTowerFn  <- CLIPVisionModel.forward ([HF] modeling_clip.py:638-651), last_hidden_state
                     without post_layernorm (model_m.py:116, quirk Q2)
+  VisionClsFn    <- the same for CLS pooling (model_m.py:122): the last layer's out-projection and MLP on the CLS rows, [B, 1, D]
   TextTowerFn    <- CLIPTextModel.forward ([HF] :513-559), last_hidden_state after final LN
   AdapterFn      <- TextAdapter/VisionAdapter.forward (adapter/clip_adapter.py:17-23, 144-150),
                     peclip.TextualAdapter (adapter/peclip.py:13-18) with ln=False
@@ -60,7 +61,7 @@ class EncoderDesc(ctypes.Structure):
                 ("act", ctypes.POINTER(LayerAct)), ("x_out", c_vp), ("workspace", c_vp),
                 ("workspace_bytes", c_i64), ("layers8", ctypes.POINTER(LayerW8)), ("q8", c_vp), ("s8", c_vp),
                 ("resid_f32", c_int), ("gemm_x3", c_int), ("x3_ws", c_vp), ("x3_ws_bytes", c_i64),
-                ("first_token", c_int)]
+                ("first_token", c_int), ("cls_last", c_int)]
 
 
 P = ctypes.POINTER
@@ -144,6 +145,11 @@ _lib.declare("clipmi_scatter_rows", [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_in
 _lib.declare("clipmi_attention_fwd", [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int])
 _lib.declare("clipmi_attention_bwd", [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                       c_int])
+_lib.declare("clipmi_attention_cls_fwd", [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, c_int])
+_lib.declare("clipmi_attention_cls_bwd", [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
+                                          c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int])
+_lib.declare("clipmi_layernorm_bwd4", [c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                       c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int])
 _lib.declare("clipmi_split3_elems", [c_int, c_int, c_int], c_i64)
 _lib.declare("clipmi_split3", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int])
 _lib.declare("clipmi_split3_colsum_ws", [c_int, c_int], c_i64)
@@ -298,10 +304,12 @@ class Encoder:
         return tab
 
     def desc(self, dtype, B, N, wbuf, acts, x_out, mask, grads=None, ws=None, fp8=False, resid32=False, x3=False,
-             first_token=False):
+             first_token=False, cls_last=False):
         """x3: the bf16x3 mode (fp32 encoder, every GEMM a split-operand bf16 product); its split-image
         scratch is allocated here and lives as long as the returned descriptor (d.x3_keep).  first_token: the
-        engine's token-0 mode (compact [B] rows; causal towers, not with fp8 / x3: the engine rejects those)."""
+        engine's token-0 mode (compact [B] rows; causal towers, not with fp8 / x3: the engine rejects those).
+        cls_last: the last layer on the CLS rows only, x_out compact [B, D] (non-causal towers, not with fp8 /
+        x3 / a mask; include/clipmi.h)."""
         t = self.t
         d = EncoderDesc()
         d.dtype, d.B, d.N, d.D, d.F = dcode(dtype), B, N, t.hidden_size, t.intermediate_size
@@ -321,6 +329,7 @@ class Encoder:
         d.act = acts
         d.x_out = x_out
         d.first_token = int(first_token)
+        d.cls_last = int(cls_last)
         if ws is not None:
             d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         if x3 and dtype == torch.float32:
@@ -370,9 +379,23 @@ def _wbuf(arena, dtype):
 
 
 # ------------------------------------------------------------------------------ vision
+def vision_cls_last(rt):
+    """Whether CLS pooling may take VisionClsFn: CLIPMI_VISION_CLS_LAST=0 forces the full tower (A/B runs, tests);
+    the fp8 towers and the bf16x3 mode keep the full last layer (the engine's cls_last mode has neither form)."""
+    return (os.environ.get("CLIPMI_VISION_CLS_LAST", "1") != "0" and not (rt.fp8 and not rt.train_tower)
+            and not getattr(rt, "x3", False))
+
+
 class VisionTowerFn(torch.autograd.Function):
+    """The vision tower's last_hidden_state [B, N, D] (no post-LayerNorm: quirk Q2)."""
+
     @staticmethod
     def forward(ctx, pixel_values, anchor, runtime):
+        return VisionTowerFn.run(ctx, pixel_values, runtime, False)
+
+    @staticmethod
+    def run(ctx, pixel_values, runtime, pooled):
+        """pooled: the engine's cls_last mode, out [B, 1, D] (VisionClsFn)."""
         rt = runtime
         arena, v, dtype = rt.arena, rt.cfg.vision_config, rt.dtype
         B = pixel_values.shape[0]
@@ -430,13 +453,13 @@ class VisionTowerFn(torch.autograd.Function):
              P_(stats0[0]), P_(stats0[1]), R, D, v.layer_norm_eps,
              arena.ptr("vision_model.embeddings.position_embedding.weight", ebuf),
              arena.ptr("vision_model.embeddings.class_embedding", ebuf), N)
-        out = torch.empty(B, N, D, dtype=xdtype, device=dev)
-        d = rt.venc.desc(dtype, B, N, wbuf, acts, out.data_ptr(), None, fp8=fp8, resid32=r32, x3=x3)
+        out = torch.empty(B, 1 if pooled else N, D, dtype=xdtype, device=dev)
+        d = rt.venc.desc(dtype, B, N, wbuf, acts, out.data_ptr(), None, fp8=fp8, resid32=r32, x3=x3, cls_last=pooled)
         _lib.check(_lib.lib().clipmi_encoder_fwd(s, ctypes.byref(d)), "clipmi_encoder_fwd")
         del d
         if train:
             ctx.rt, ctx.B, ctx.buf, ctx.acts, ctx.X, ctx.h0, ctx.stats0 = rt, B, buf, acts, X, h0, stats0
-            ctx.r32 = r32
+            ctx.r32, ctx.pooled = r32, pooled
         else:
             del buf
         return out
@@ -452,9 +475,14 @@ class VisionTowerFn(torch.autograd.Function):
         dc = dcode(dtype)
         arena.prepare_grads()
         wbuf = _wbuf(arena, dtype)
-        dx = dout.to(dtype).contiguous().clone()
+        if ctx.pooled:  # the engine reads dL/d(out) [B, D] from the head of the [R, D] buffer it returns dx in
+            dx = torch.empty(R, D, dtype=dtype, device=dev)
+            dx[:B].copy_(dout.reshape(B, D))
+        else:
+            dx = dout.to(dtype).contiguous().clone()
         x3 = getattr(rt, "x3", False)
-        d = rt.venc.desc(dtype, B, N, wbuf, ctx.acts, None, None, grads=rt.venc.grads(), resid32=ctx.r32, x3=x3)
+        d = rt.venc.desc(dtype, B, N, wbuf, ctx.acts, None, None, grads=rt.venc.grads(), resid32=ctx.r32, x3=x3,
+                         cls_last=ctx.pooled)
         ws = _ws(_lib.lib().clipmi_encoder_bwd_ws(ctypes.byref(d)), dev)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         hook = _grad_hook(rt)
@@ -504,6 +532,18 @@ class VisionTowerFn(torch.autograd.Function):
         # fresh device mallocs mid-step); stream-ordered reuse keeps the queued kernels safe
         ctx.buf = ctx.acts = ctx.X = ctx.h0 = ctx.stats0 = None
         return None, None, None
+
+
+class VisionClsFn(VisionTowerFn):
+    """VisionTowerFn for CLS pooling (model_m.py:116-122, no post-LayerNorm: quirk Q2): only row 0 of the last
+    encoder layer's output is read, so the engine runs that layer's out-projection and MLP on the B CLS rows (its
+    cls_last mode, include/clipmi.h); the layer's attention still runs on every row, each a key and a value.
+    Returns [B, 1, D] in the residual dtype, bitwise the value of VisionTowerFn(...)[:, :1]; the backward gives the full
+    tower's parameter gradients for a loss that reads the CLS row alone."""
+
+    @staticmethod
+    def forward(ctx, pixel_values, anchor, runtime):
+        return VisionTowerFn.run(ctx, pixel_values, runtime, True)
 
 
 # ------------------------------------------------------------------------------ text

@@ -18,6 +18,9 @@
 // first_token (causal encoders pooled at token 0, model_m.py:102): token 0 attends only to
 // itself, so the engine runs that row alone -- B compact rows, qkv reduced to the V projection,
 // o = V (no q, k, softmax or attention launch), the rest as above; see include/clipmi.h.
+// cls_last (the vision tower pooled at CLS without a post-LayerNorm, model_m.py:116-122): only row 0 of the last
+// layer's output is read, so that layer runs as usual through the attention (every row is a key and a value) and its
+// out-projection and MLP on the B CLS rows; see include/clipmi.h.
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
@@ -40,6 +43,9 @@ int clipmi_colsum(void*, int, const void*, int64_t, int, int, float*, int, void*
 int clipmi_attention_fwd(void*, int, const void*, void*, float*, const int64_t*, int, int, int, int, int);
 int clipmi_attention_bwd(void*, int, const void*, const void*, const float*, const void*, void*, const int64_t*, int,
                          int, int, int, int);
+int clipmi_layernorm_bwd4(void*, int, int, int, const void*, int64_t, const void*, int64_t, const float*, const float*,
+                          const void*, void*, int64_t, const void*, int64_t, int, float*, float*, int, void*, int64_t,
+                          int, int);
 int clipmi_quant_mxfp8(void*, int, const void*, int64_t, int64_t, int, uint8_t*, uint8_t*);
 int clipmi_attention_fwd_x3(void*, const void*, void*, float*, const int64_t*, int, int, int, int, int);
 int clipmi_attention_bwd_x3(void*, const void*, const void*, const float*, const void*, void*, const int64_t*, int,
@@ -233,6 +239,13 @@ WsPlan plan(const clipmi_encoder_desc* d) {
     const int s = (d->gemm_x3 && d->dtype == CLIPMI_F32) ? 1 : wgrad_splits(sh[0], sh[1], (int)R, d->dtype);
     if (s > 1) sp = std::max<int64_t>(sp, (int64_t)s * sh[0] * (sh[1] + 1) * 4);  // slabs + bias partials
   }
+  if (d->cls_last) {  // the last layer's out-projection / MLP weight gradients sum over the B CLS rows
+    const int cshapes[3][3] = {{d->D, d->D, d->B}, {d->F, d->D, d->B}, {d->D, d->F, d->B}};
+    for (auto& sh : cshapes) {
+      const int s = wgrad_splits(sh[0], sh[1], sh[2], d->dtype);
+      if (s > 1) sp = std::max<int64_t>(sp, (int64_t)s * sh[0] * (sh[1] + 1) * 4);
+    }
+  }
   // bf16: two slab regions used alternately, so a weight gradient's split-K sum can be deferred into the
   // next persistent GEMM while the following weight gradient writes its own slabs (DeferredReduce)
   if (d->dtype == CLIPMI_BF16) sp = 2 * align256(sp);
@@ -292,6 +305,12 @@ int pending_hazard(const DeferredReduce& r, const void* dst, int64_t bytes, cons
 int validate(const clipmi_encoder_desc* d) {
   CLIPMI_REQUIRE(d && d->layers && d->act, "null descriptor");
   CLIPMI_REQUIRE(d->dtype == CLIPMI_BF16 || d->dtype == CLIPMI_F32 || d->dtype == CLIPMI_FP8, "dtype");
+  CLIPMI_REQUIRE(!d->cls_last || !d->first_token, "cls_last: not with first_token");
+  CLIPMI_REQUIRE(!d->cls_last || !d->causal, "cls_last: not with a causal encoder (such towers use first_token)");
+  CLIPMI_REQUIRE(!d->cls_last || d->dtype != CLIPMI_FP8, "cls_last: not with the fp8 encoder (CLIPMI_FP8)");
+  CLIPMI_REQUIRE(!d->cls_last || !d->gemm_x3, "cls_last: not with gemm_x3");
+  CLIPMI_REQUIRE(!d->cls_last || !d->attention_mask, "cls_last: not with an attention_mask");
+  CLIPMI_REQUIRE(!d->cls_last || d->N <= 4096, "cls_last: N <= 4096");
   CLIPMI_REQUIRE(!d->first_token || d->causal, "first_token needs a causal encoder (token 0 must attend only to itself)");
   CLIPMI_REQUIRE(!d->first_token || d->dtype != CLIPMI_FP8, "first_token: not with the fp8 encoder");
   CLIPMI_REQUIRE(!d->first_token || !d->gemm_x3, "first_token: not with gemm_x3");
@@ -517,6 +536,23 @@ extern "C" int clipmi_encoder_fwd(void* s, const clipmi_encoder_desc* d) {
     void* x_out = (l + 1 < d->L) ? d->act[l + 1].x_in : d->x_out;
     CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.x_in, D, a.ln1, D, w.ln1_w, w.ln1_b, a.mean1, a.rstd1, R, D, d->eps,
                                      nullptr, nullptr, 0));
+    if (d->cls_last && l == d->L - 1) {  // only the CLS rows of this layer's output are read (clipmi.h cls_last):
+      // the layer runs as usual through the attention (every row is a key and a value, and the same kernels keep the
+      // CLS row's bits), then on the B CLS rows, read in place with a leading dimension of N * D
+      const int B = d->B;
+      const int64_t ldcls = (int64_t)d->N * D;
+      CLIPMI_TRY(gemm(s, dt, R, 3 * D, D, a.ln1, D, true, w.qkv_w, D, true, a.qkv, 3 * D, dt, CLIPMI_EPI_BIAS, w.qkv_b));
+      CLIPMI_TRY(clipmi_attention_fwd(s, dt, a.qkv, a.o, a.lse, nullptr, 0, B, d->H, d->N, D));
+      CLIPMI_TRY(gemm(s, dt, B, D, D, a.o, ldcls, true, w.out_w, D, true, a.h, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
+                      w.out_b, a.x_in, ldcls));
+      CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.h, D, a.ln2, D, w.ln2_w, w.ln2_b, a.mean2, a.rstd2, B, D, d->eps,
+                                       nullptr, nullptr, 0));
+      const int f1 = CLIPMI_EPI_BIAS | CLIPMI_EPI_QGELU | (a.pre ? CLIPMI_EPI_STORE_DACT : 0);
+      CLIPMI_TRY(gemm(s, dt, B, F, D, a.ln2, D, true, w.fc1_w, D, true, a.act, F, dt, f1, w.fc1_b, nullptr, 0, a.pre, F));
+      CLIPMI_TRY(gemm(s, dt, B, D, F, a.act, F, true, w.fc2_w, F, true, x_out, D, xdt,
+                      CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID, w.fc2_b, a.h, D));
+      continue;
+    }
     const void* o = a.o;
     if (d->first_token) {  // token 0 sees one key, itself: O = V (0 where that key is padded), no q, k or softmax
       const size_t es = esize(dt);
@@ -588,18 +624,19 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
   int wg_no = 0;
   // wgrad: C[M,N] += sum_tokens A[t][m] B[t][n]; the bf16 path also fuses the Linear bias
   // gradient (sum_tokens A[t][m]) into the same GEMM, fp32 uses a column-sum pass
-  auto wgrad = [&](int M, int N, const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
+  // (Kt tokens: R, or the B CLS rows of a cls_last layer)
+  auto wgrad = [&](int Kt, int M, int N, const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
                    float* bgrad) -> int {
-    const int sp = wgrad_splits(M, N, R, d->dtype);
+    const int sp = wgrad_splits(M, N, Kt, d->dtype);
     const bool fuse = dt == CLIPMI_BF16;
     char* wsl = (char*)wsplit + (dt == CLIPMI_BF16 ? (wg_no++ & 1) * region : 0);
     // an outstanding split-K sum still reading this region runs first (not reached with the alternation)
     if (pend.kind == 1 && (const char*)pend.ws >= wsl && (const char*)pend.ws < wsl + region)
       CLIPMI_TRY(launch_deferred((hipStream_t)s, pend));
     CLIPMI_TRY(pending_hazard(pend, wsl, region, "a weight gradient's split-K slabs"));
-    CLIPMI_TRY(gemm(s, dt, M, N, R, A, lda, false, B, ldb, false, C, N, f32, CLIPMI_EPI_BETA, nullptr, nullptr, 0,
+    CLIPMI_TRY(gemm(s, dt, M, N, Kt, A, lda, false, B, ldb, false, C, N, f32, CLIPMI_EPI_BETA, nullptr, nullptr, 0,
                     nullptr, 0, sp, wsl, region, fuse ? bgrad : nullptr));
-    if (!fuse) CLIPMI_TRY(clipmi_colsum(s, dt, A, lda, R, M, bgrad, 1, wcol, col_bytes));
+    if (!fuse) CLIPMI_TRY(clipmi_colsum(s, dt, A, lda, Kt, M, bgrad, 1, wcol, col_bytes));
     return CLIPMI_OK;
   };
   // LayerNorm backward rewrites the partial rows an outstanding affine sum reads: run that one first
@@ -623,11 +660,36 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
     const clipmi_layer_act& a = d->act[l];
     const clipmi_layer_grad& g = d->grads[l];
     CLIPMI_REQUIRE(a.pre, "training forward must save pre-activations");
+    if (d->cls_last && l == d->L - 1) {  // the forward ran this layer's out-projection and MLP for the CLS rows only
+      // (clipmi.h cls_last): dx holds dL/dx_out [B][D] in its head; the MLP and out-projection branches are the full
+      // layer's on B rows, the attention branch the full layer's with d_o zero at every other row
+      const int B = d->B;
+      const int64_t ldcls = (int64_t)d->N * D;
+      CLIPMI_TRY(gemm(s, dt, B, F, D, dx, D, true, w.fc2_w, F, false, dbig, F, dt, CLIPMI_EPI_MUL_AUX, nullptr,
+                      nullptr, 0, a.pre, F));                                            // d_pre
+      CLIPMI_TRY(wgrad(B, D, F, dx, D, a.act, F, g.fc2_w, g.fc2_b));                     // gW2, gb2
+      CLIPMI_TRY(wgrad(B, F, D, dbig, F, a.ln2, D, g.fc1_w, g.fc1_b));                   // gW1, gb1
+      CLIPMI_TRY(gemm(s, dt, B, D, F, dbig, F, true, w.fc1_w, D, false, dln, D, dt, 0)); // d_ln2
+      CLIPMI_TRY(ln_guard());
+      CLIPMI_TRY(clipmi_layernorm_bwd2(s, xdt, dt, dln, D, a.h, D, a.mean2, a.rstd2, w.ln2_w, g2, D, dx, D, g.ln2_w,
+                                       g.ln2_b, 1, wln, ln_bytes, B, D));                // dh [B][D]
+      CLIPMI_TRY(wgrad(B, D, D, g2, D, a.o, ldcls, g.out_w, g.out_b));                   // gWo += dh^T o_cls
+      // d_o [R][D]: dh Wo at the CLS rows, zero elsewhere (those rows' outputs were not read)
+      CLIPMI_HIP(hipMemsetAsync(dln, 0, (size_t)R * D * esize(dt), (hipStream_t)s));
+      CLIPMI_TRY(gemm(s, dt, B, D, D, g2, D, true, w.out_w, D, false, dln, ldcls, dt, 0));
+      CLIPMI_TRY(clipmi_attention_bwd(s, dt, a.qkv, a.o, a.lse, dln, dbig, nullptr, 0, B, d->H, d->N, D));  // d_qkv
+      CLIPMI_TRY(wgrad(R, 3 * D, D, dbig, 3 * D, a.ln1, D, g.qkv_w, g.qkv_b));           // gWqkv += d_qkv^T ln1
+      CLIPMI_TRY(gemm(s, dt, R, D, 3 * D, dbig, 3 * D, true, w.qkv_w, D, false, dln, D, dt, 0));  // d_ln1
+      CLIPMI_TRY(ln_guard());
+      CLIPMI_TRY(clipmi_layernorm_bwd4(s, xdt, dt, dt, dln, D, a.x_in, D, a.mean1, a.rstd1, w.ln1_w, dx, D, g2, D, d->N,
+                                       g.ln1_w, g.ln1_b, 1, wln, ln_bytes, R, D));       // dx_in = [dh at CLS] + LN1'
+      continue;
+    }
     // MLP branch: dx is dL/dy
     CLIPMI_TRY(gemm(s, dt, R, F, D, dx, D, true, w.fc2_w, F, false, dbig, F, dt, CLIPMI_EPI_MUL_AUX, nullptr, nullptr,
                     0, a.pre, F));                                          // d_pre = (dx W2) * qgelu'(pre)
-    CLIPMI_TRY(wgrad(D, F, dx, D, a.act, F, g.fc2_w, g.fc2_b));            // gW2 += dx^T act, gb2 += sum dx
-    CLIPMI_TRY(wgrad(F, D, dbig, F, a.ln2, D, g.fc1_w, g.fc1_b));          // gW1 += d_pre^T ln2
+    CLIPMI_TRY(wgrad(R, D, F, dx, D, a.act, F, g.fc2_w, g.fc2_b));            // gW2 += dx^T act, gb2 += sum dx
+    CLIPMI_TRY(wgrad(R, F, D, dbig, F, a.ln2, D, g.fc1_w, g.fc1_b));          // gW1 += d_pre^T ln2
     CLIPMI_TRY(gemm(s, dt, R, D, F, dbig, F, true, w.fc1_w, D, false, dln, D, dt, 0));  // d_ln2 = d_pre W1
     CLIPMI_TRY(ln_guard());
     CLIPMI_TRY(clipmi_layernorm_bwd2(s, xdt, dt, dln, D, a.h, D, a.mean2, a.rstd2, w.ln2_w, g2, D, dx, D, g.ln2_w,
@@ -637,17 +699,17 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
     const void* dln1 = dln;
     if (d->first_token) {  // O is V (act[l].qkv, row-selected): dV = d_o with the same select; the q / k slots of
                            // gWqkv / gbqkv are left alone (their gradient is exactly zero)
-      CLIPMI_TRY(wgrad(D, D, g2, D, a.qkv, D, g.out_w, g.out_b));                        // gWo += dh^T o
+      CLIPMI_TRY(wgrad(R, D, D, g2, D, a.qkv, D, g.out_w, g.out_b));                        // gWo += dh^T o
       CLIPMI_TRY(select_rows(s, d, dln));                                                 // dV
-      CLIPMI_TRY(wgrad(D, D, dln, D, a.ln1, D, g.qkv_w + (size_t)2 * D * D, g.qkv_b + 2 * D));  // gWv += dV^T ln1
+      CLIPMI_TRY(wgrad(R, D, D, dln, D, a.ln1, D, g.qkv_w + (size_t)2 * D * D, g.qkv_b + 2 * D));  // gWv += dV^T ln1
       CLIPMI_TRY(gemm(s, dt, R, D, D, dln, D, true, (const char*)w.qkv_w + (size_t)2 * D * D * esize(dt), D, false,
                       dbig, D, dt, 0));                                                   // d_ln1 = dV Wv
       dln1 = dbig;
     } else {
-      CLIPMI_TRY(wgrad(D, D, g2, D, a.o, D, g.out_w, g.out_b));                          // gWo += dh^T o
+      CLIPMI_TRY(wgrad(R, D, D, g2, D, a.o, D, g.out_w, g.out_b));                          // gWo += dh^T o
       CLIPMI_TRY(clipmi_attention_bwd(s, dt, a.qkv, a.o, a.lse, dln, dbig, d->attention_mask, d->causal, d->B, d->H,
                                       d->N, D));                            // d_qkv
-      CLIPMI_TRY(wgrad(3 * D, D, dbig, 3 * D, a.ln1, D, g.qkv_w, g.qkv_b));  // gWqkv += d_qkv^T ln1
+      CLIPMI_TRY(wgrad(R, 3 * D, D, dbig, 3 * D, a.ln1, D, g.qkv_w, g.qkv_b));  // gWqkv += d_qkv^T ln1
       CLIPMI_TRY(gemm(s, dt, R, D, 3 * D, dbig, 3 * D, true, w.qkv_w, D, false, dln, D, dt, 0));  // d_ln1
     }
     CLIPMI_TRY(ln_guard());

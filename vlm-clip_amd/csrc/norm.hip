@@ -181,7 +181,7 @@ template <typename TX, typename T, int PS, int NP, typename TW = T, bool X3 = fa
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* dy, int64_t lddy, const TX* x, int64_t ldx,
                                                      const float* mean, const float* rstd, const TW* w,
                                                      T* dx, int64_t lddx, const T* dres, int64_t ldres,
-                                                     float* ws, int R, int D, bf16* img) {
+                                                     float* ws, int R, int D, bf16* img, int res_period) {
   constexpr int NPR = X3 ? 3 : 2;
   __shared__ float red[4][NPR][NP * PS * 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -204,15 +204,19 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* dy, int64_t lddy, 
   for (int row0 = (blockIdx.x * 4 + wave) * RPW; row0 < R; row0 += gridDim.x * 4 * RPW) {
     float g[RPW][NP][PS], xh[RPW][NP][PS], rr[RPW][NP][PS], d[RPW][NP][PS];
     float mu[RPW], rs[RPW];
+    bool has_res[RPW];
 #pragma unroll
     for (int q = 0; q < RPW; ++q) {
       const int row = min(row0 + q, R - 1);  // a clamped duplicate row is computed, not stored
       mu[q] = mean[row];
       rs[q] = rstd[row];
+      // res_period > 0: dres is compact, row b of it belongs to row b * res_period (the other rows add nothing)
+      const int rrow = res_period > 0 ? row / res_period : row;
+      has_res[q] = dres && (res_period <= 0 || rrow * res_period == row);
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
         const int c = (k * 64 + lane) * PS;
-        if (dres) vload<T, PS>(dres + (int64_t)row * ldres + c, rr[q][k]);
+        if (has_res[q]) vload<T, PS>(dres + (int64_t)rrow * ldres + c, rr[q][k]);
         vload<T, PS>(dy + (int64_t)row * lddy + c, d[q][k]);
         vload<TX, PS>(x + (int64_t)row * ldx + c, xh[q][k]);
       }
@@ -245,7 +249,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* dy, int64_t lddy, 
 #pragma unroll
         for (int j = 0; j < PS; ++j) {
           o[j] = rs[q] * (g[q][k][j] - s1 - xh[q][k][j] * s2);
-          if (dres) o[j] += rr[q][k][j];
+          if (has_res[q]) o[j] += rr[q][k][j];
         }
         vstore<T, PS>(dx + (int64_t)row * lddx + c, o);
         if constexpr (X3) {
@@ -318,7 +322,7 @@ template <typename TX, typename T, typename TW = T>
 __global__ __launch_bounds__(256) void ln_bwd_any_kernel(const T* dy, int64_t lddy, const TX* x, int64_t ldx,
                                                          const float* mean, const float* rstd, const TW* w, T* dx,
                                                          int64_t lddx, const T* dres, int64_t ldres, float* ws, int R,
-                                                         int D) {
+                                                         int D, int res_period) {
   extern __shared__ float red_any[];  // [4 waves][2][D] when ws
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* pg = red_any + (int64_t)wave * 2 * D;
@@ -329,6 +333,8 @@ __global__ __launch_bounds__(256) void ln_bwd_any_kernel(const T* dy, int64_t ld
     const float mu = mean[row], rs = rstd[row];
     const T* dyr = dy + (int64_t)row * lddy;
     const TX* xr = x + (int64_t)row * ldx;
+    const int rrow = res_period > 0 ? row / res_period : row;  // compact dres (see ln_bwd_kernel)
+    const bool has_res = dres && (res_period <= 0 || rrow * res_period == row);
     float s1 = 0.f, s2 = 0.f;
     for (int c = lane; c < D; c += 64) {
       const float g = (float)dyr[c] * (float)w[c];
@@ -340,7 +346,7 @@ __global__ __launch_bounds__(256) void ln_bwd_any_kernel(const T* dy, int64_t ld
     for (int c = lane; c < D; c += 64) {
       const float d = (float)dyr[c], xh = ((float)xr[c] - mu) * rs;
       float o = rs * (d * (float)w[c] - s1 - xh * s2);
-      if (dres) o += (float)dres[(int64_t)row * ldres + c];
+      if (has_res) o += (float)dres[(int64_t)rrow * ldres + c];
       dx[(int64_t)row * lddx + c] = (T)o;
       if (ws) {
         pg[c] += d * xh;
@@ -708,7 +714,7 @@ void ln_fwd_q8_launch(hipStream_t s, void* x, int64_t ldx, uint8_t* q8, uint8_t*
 template <typename TX, typename T, int PS, int NP, typename TW = T, bool X3 = false>
 void ln_bwd_launch(hipStream_t s, int& grid, const void* dy, int64_t lddy, const void* x, int64_t ldx,
                    const float* mean, const float* rstd, const void* w, void* dx, int64_t lddx, const void* dres,
-                   int64_t ldres, float* ws, int R, int D, void* img = nullptr) {
+                   int64_t ldres, float* ws, int R, int D, void* img = nullptr, int res_period = 0) {
   static int resident = [] {
     int per_cu = 0, dev = 0, cus = 0;
     (void)hipGetDevice(&dev);
@@ -721,7 +727,7 @@ void ln_bwd_launch(hipStream_t s, int& grid, const void* dy, int64_t lddy, const
   if (grid > resident) grid = resident;
   hipLaunchKernelGGL((ln_bwd_kernel<TX, T, PS, NP, TW, X3>), dim3(grid), dim3(256), 0, s, (const T*)dy, lddy,
                      (const TX*)x, ldx, mean, rstd, (const TW*)w, (T*)dx, lddx, (const T*)dres, ldres, ws, R, D,
-                     (bf16*)img);
+                     (bf16*)img, res_period);
 }
 // the bf16x3 form (fp32 everything, dx's image + column sums)
 template <typename TX, typename T, int PS, int NP>
@@ -731,11 +737,21 @@ void ln_bwd_x3_launch(hipStream_t s, int& grid, const void* dy, int64_t lddy, co
   ln_bwd_launch<TX, T, PS, NP, T, true>(s, grid, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, ws, R, D, img);
 }
 
+// the plain form (dtype == w_dtype) with the period given
+template <typename TX, typename T, int PS, int NP>
+void ln_bwd_launch_p(hipStream_t s, int& grid, const void* dy, int64_t lddy, const void* x, int64_t ldx,
+                     const float* mean, const float* rstd, const void* w, void* dx, int64_t lddx, const void* dres,
+                     int64_t ldres, float* ws, int R, int D, int res_period) {
+  ln_bwd_launch<TX, T, PS, NP>(s, grid, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, ws, R, D, nullptr,
+                               res_period);
+}
+
 template <typename TX, typename T, int PS, int NP>
 void ln_bwd_launch_w32(hipStream_t s, int& grid, const void* dy, int64_t lddy, const void* x, int64_t ldx,
                        const float* mean, const float* rstd, const void* w, void* dx, int64_t lddx, const void* dres,
-                       int64_t ldres, float* ws, int R, int D) {
-  ln_bwd_launch<TX, T, PS, NP, float>(s, grid, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, ws, R, D);
+                       int64_t ldres, float* ws, int R, int D, int res_period) {
+  ln_bwd_launch<TX, T, PS, NP, float>(s, grid, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, ws, R, D, nullptr,
+                                      res_period);
 }
 
 // the widths the register-resident kernels take
@@ -855,7 +871,7 @@ extern "C" int64_t clipmi_layernorm_bwd_ws(int R, int D) {
 template <typename TX, typename T, typename TW = T>
 static int ln_bwd_t(hipStream_t s, int& nb, const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* mean,
                     const float* rstd, const void* w, void* dx, int64_t lddx, const void* dres, int64_t ldres, float* wsf,
-                    int R, int D) {
+                    int R, int D, int res_period) {
   const int ps = ln_ps(D);
   const bool vec = ln_aligned<T>(dy, lddy, ps) && ln_aligned<TX>(x, ldx, ps) && ln_aligned<TW>(w, 0, ps) &&
                    ln_aligned<T>(dx, lddx, ps) && (!dres || ln_aligned<T>(dres, ldres, ps));
@@ -863,13 +879,15 @@ static int ln_bwd_t(hipStream_t s, int& nb, const void* dy, int64_t lddy, const 
     const size_t lds = wsf ? (size_t)4 * 2 * D * 4 : 0;
     (void)lds_optin((const void*)ln_bwd_any_kernel<TX, T, TW>, (int)lds);
     hipLaunchKernelGGL((ln_bwd_any_kernel<TX, T, TW>), dim3(nb), dim3(256), lds, s, (const T*)dy, lddy, (const TX*)x, ldx,
-                       mean, rstd, (const TW*)w, (T*)dx, lddx, (const T*)dres, ldres, wsf, R, D);
+                       mean, rstd, (const TW*)w, (T*)dx, lddx, (const T*)dres, ldres, wsf, R, D, res_period);
     return CLIPMI_OK;
   }
   if constexpr (std::is_same<TW, T>::value)
-    LN_DISPATCH(D, ln_bwd_launch, TX, T, s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D);
+    LN_DISPATCH(D, ln_bwd_launch_p, TX, T, s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D,
+                res_period);
   else
-    LN_DISPATCH(D, ln_bwd_launch_w32, TX, T, s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D);
+    LN_DISPATCH(D, ln_bwd_launch_w32, TX, T, s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D,
+                res_period);
   return CLIPMI_OK;
 }
 
@@ -895,7 +913,18 @@ extern "C" int clipmi_layernorm_bwd3(void* stream, int x_dtype, int dtype, int w
                                      const void* x, int64_t ldx, const float* mean, const float* rstd, const void* w,
                                      void* dx, int64_t lddx, const void* dres, int64_t ldres, float* dw, float* db,
                                      int beta_wb, void* ws, int64_t ws_bytes, int R, int D) {
+  return clipmi_layernorm_bwd4(stream, x_dtype, dtype, w_dtype, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres,
+                               0, dw, db, beta_wb, ws, ws_bytes, R, D);
+}
+
+// res_period > 0: dres is compact [ceil(R / res_period)][ldres] and its row b is added to row b * res_period alone
+// (the engine's cls_last layer: the residual gradient exists at the CLS rows only; no zero-filled [R][D] tensor)
+extern "C" int clipmi_layernorm_bwd4(void* stream, int x_dtype, int dtype, int w_dtype, const void* dy, int64_t lddy,
+                                     const void* x, int64_t ldx, const float* mean, const float* rstd, const void* w,
+                                     void* dx, int64_t lddx, const void* dres, int64_t ldres, int res_period, float* dw,
+                                     float* db, int beta_wb, void* ws, int64_t ws_bytes, int R, int D) {
   hipStream_t s = (hipStream_t)stream;
+  CLIPMI_REQUIRE(res_period >= 0, "layernorm: res_period >= 0");
   CLIPMI_REQUIRE(ln_types_ok(x_dtype, dtype), "layernorm: dtypes (equal, or fp32 x with bf16 gradients)");
   CLIPMI_REQUIRE(w_dtype == dtype || (w_dtype == CLIPMI_F32 && x_dtype == CLIPMI_F32),
                  "layernorm: weight dtype (the gradients', or fp32 with fp32 x)");
@@ -906,11 +935,11 @@ extern "C" int clipmi_layernorm_bwd3(void* stream, int x_dtype, int dtype, int w
   float* wsf = (dw || db) ? (float*)ws : nullptr;
   if (wsf) CLIPMI_REQUIRE(ws_bytes >= (int64_t)nb * 2 * D * 4, "layernorm_bwd workspace too small");
   // the fast kernels shrink nb to the resident block count (the partial rows they write)
-  if (dtype == CLIPMI_F32) CLIPMI_TRY((ln_bwd_t<float, float>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D)));
+  if (dtype == CLIPMI_F32) CLIPMI_TRY((ln_bwd_t<float, float>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D, res_period)));
   else if (x_dtype == CLIPMI_F32 && w_dtype == CLIPMI_F32)
-    CLIPMI_TRY((ln_bwd_t<float, bf16, float>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D)));
-  else if (x_dtype == CLIPMI_F32) CLIPMI_TRY((ln_bwd_t<float, bf16>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D)));
-  else CLIPMI_TRY((ln_bwd_t<bf16, bf16>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D)));
+    CLIPMI_TRY((ln_bwd_t<float, bf16, float>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D, res_period)));
+  else if (x_dtype == CLIPMI_F32) CLIPMI_TRY((ln_bwd_t<float, bf16>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D, res_period)));
+  else CLIPMI_TRY((ln_bwd_t<bf16, bf16>(s, nb, dy, lddy, x, ldx, mean, rstd, w, dx, lddx, dres, ldres, wsf, R, D, res_period)));
   CLIPMI_CHECK_LAUNCH();
   if (((uintptr_t)wsf & 15) != 0 || D % 4 != 0) {
     if (dw) hipLaunchKernelGGL(reduce_partials_kernel, dim3((D + 63) / 64), dim3(1024), 0, s, wsf, (int64_t)2 * D, nb, D, dw, beta_wb);
