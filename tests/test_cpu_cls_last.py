@@ -71,6 +71,49 @@ def test_bwd_ws_is_at_least_the_full_modes():
         assert cls >= full
 
 
+# clipmi_encoder_bwd_ws per (dtype, mode, B, N), recorded from the commit before the engine's layer bodies and plan()'s
+# weight-gradient shape tables were merged, on a machine without a GPU.  The bf16 split choice reads the device's CU
+# count, which falls back to 256 without a device: an MI355X's own count, so the table holds on both.
+# D, F, H = 128, 512, 2; 768, 3072, 12 at (1024, 197).
+BWD_WS = {
+    ("F32", "full", 5, 50): 866816,
+    ("F32", "full", 33, 50): 6510080,
+    ("F32", "full", 1100, 2): 8678400,
+    ("F32", "full", 1024, 197): 3750515712,
+    ("F32", "first_token", 5, 50): 20480,
+    ("F32", "first_token", 33, 50): 117248,
+    ("F32", "first_token", 1100, 2): 4340224,
+    ("F32", "first_token", 1024, 197): 35457024,
+    ("F32", "cls_last", 5, 50): 866816,
+    ("F32", "cls_last", 33, 50): 6510080,
+    ("F32", "cls_last", 1100, 2): 8678400,
+    ("F32", "cls_last", 1024, 197): 3750515712,
+    ("BF16", "full", 5, 50): 482816,
+    ("BF16", "full", 33, 50): 3183104,
+    ("BF16", "full", 1100, 2): 4242432,
+    ("BF16", "full", 1024, 197): 2007146496,
+    ("BF16", "first_token", 5, 50): 12800,
+    ("BF16", "first_token", 33, 50): 66560,
+    ("BF16", "first_token", 1100, 2): 2122240,
+    ("BF16", "first_token", 1024, 197): 11845632,
+    ("BF16", "cls_last", 5, 50): 482816,
+    ("BF16", "cls_last", 33, 50): 3183104,
+    ("BF16", "cls_last", 1100, 2): 4242432,
+    ("BF16", "cls_last", 1024, 197): 2007146496,
+}
+
+
+@pytest.mark.parametrize("key", list(BWD_WS), ids=lambda k: "-".join(map(str, k)))
+def test_bwd_ws_matches_recorded_table(key):
+    dt, mode, b, n = key
+    d = T.EncoderDesc()
+    d.dtype, d.B, d.N, d.L, d.eps = getattr(_lib, dt), b, n, L, 1e-5
+    d.D, d.F, d.H = (768, 3072, 12) if (b, n) == (1024, 197) else (D, F, H)
+    d.causal = d.first_token = int(mode == "first_token")
+    d.cls_last = int(mode == "cls_last")
+    assert int(_lib.lib().clipmi_encoder_bwd_ws(ctypes.byref(d))) == BWD_WS[key]
+
+
 P = 4096  # a non-null, 16-byte aligned address; no call below may reach the device
 
 

@@ -13,7 +13,6 @@ tests/test_gpu_first_token.py.  Measured figures (MI355X) are recorded in DESIGN
 activation bits, so the errors are the full engine's."""
 import ctypes
 import math
-import types
 
 import numpy as np
 import pytest
@@ -22,6 +21,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import kernel_checks as kc  # noqa: E402
+from engine_harness import D, EPS, H, MODES, errors, inputs, make_weights  # noqa: E402
+from engine_harness import run_engine as run  # noqa: E402
 import test_gpu_structured as sg  # noqa: E402  (the bounds of the structured attention tests)
 from kernel_checks import guarded, guarded1d, integer_tensor  # noqa: E402
 
@@ -174,80 +175,10 @@ def test_cls_attention_one_dominating_key(N, H, B, dtype):
 
 
 # ================================================================================================ B. engine
-D, H, F = 128, 2, 512
-EPS = 1e-5
-SHAPES = {"ln1_w": (D,), "ln1_b": (D,), "qkv_w": (3 * D, D), "qkv_b": (3 * D,), "out_w": (D, D), "out_b": (D,),
-          "ln2_w": (D,), "ln2_b": (D,), "fc1_w": (F, D), "fc1_b": (F,), "fc2_w": (D, F), "fc2_b": (D,)}
-MODES = {"fp32": (torch.float32, False), "bf16": (torch.bfloat16, False), "bf16_resid32": (torch.bfloat16, True)}
-
-
-def make_weights(seed, dtype, L):
-    g = torch.Generator().manual_seed(seed)
-    out = []
-    for _ in range(L):
-        w = {}
-        for n, shp in SHAPES.items():
-            t = torch.randn(shp, generator=g)
-            if n in ("ln1_w", "ln2_w"):
-                t = 1.0 + 0.1 * t
-            elif n.endswith("_w"):
-                t = t / shp[1] ** 0.5
-            else:
-                t = 0.1 * t
-            w[n] = t.to(dtype).cuda().contiguous()
-        out.append(w)
-    return out
-
-
 def run_engine(cls, dtype, r32, B, N, L, weights, x0, dy0, grad_fill=None, chunks=None):
-    """One forward + backward of the native engine.  x0 [B, N, D] fp32, dy0 [B, D]: the upstream gradient at the CLS
-    row (zero elsewhere).  Returns (output at the CLS row, dx [B, N, D], {layer.name: gradient}), fp32 on the device.
-    chunks: the backward as clipmi_encoder_bwd_layers calls over these (hi, lo) ranges instead of one call."""
-    dev = x0.device
-    xdt = torch.float32 if r32 else dtype
-    R = B * N
-    tcfg = types.SimpleNamespace(hidden_size=D, intermediate_size=F, num_attention_heads=H, num_hidden_layers=L,
-                                 layer_norm_eps=EPS)
-    enc = T.Encoder(None, "vision_model", tcfg, causal=False)
-    buf, acts = enc.alloc(B, N, dtype, dev, True, resid32=r32)
-    x_in = x0.reshape(R, D).to(xdt).contiguous()
-    acts[0].x_in = x_in.data_ptr()
-    wt, gt = (T.LayerW * L)(), (T.LayerG * L)()
-    grads = []
-    for l in range(L):
-        gl = {}
-        for n, shp in SHAPES.items():
-            setattr(wt[l], n, weights[l][n].data_ptr())
-            gl[n] = (torch.zeros(shp, dtype=torch.float32, device=dev) if grad_fill is None
-                     else grad_fill[f"{l}.{n}"].clone())
-            setattr(gt[l], n, gl[n].data_ptr())
-        grads.append(gl)
-    x_out = torch.empty(B if cls else R, D, dtype=xdt, device=dev)
-    d = T.EncoderDesc()
-    d.dtype, d.B, d.N, d.D, d.F, d.H, d.L, d.eps, d.causal = T.dcode(dtype), B, N, D, F, H, L, EPS, 0
-    d.layers, d.grads, d.act, d.x_out = wt, gt, acts, x_out.data_ptr()
-    d.resid_f32, d.cls_last = int(r32), int(cls)
-    s = K.stream()
-    lib = _lib.lib()
-    _lib.check(lib.clipmi_encoder_fwd(s, ctypes.byref(d)), "clipmi_encoder_fwd")
-    ws = torch.empty(max(int(lib.clipmi_encoder_bwd_ws(ctypes.byref(d))), 16), dtype=torch.uint8, device=dev)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    if cls:  # dL/dx_out in the head of the [R, D] buffer; the rest is overwritten (NaN until then)
-        dx = torch.full((R, D), float("nan"), dtype=dtype, device=dev)
-        dx[:B] = dy0.to(dtype)
-    else:
-        dx = torch.zeros(B, N, D, dtype=dtype, device=dev)
-        dx[:, 0] = dy0.to(dtype)
-        dx = dx.reshape(R, D)
-    if chunks is None:
-        _lib.check(lib.clipmi_encoder_bwd(s, ctypes.byref(d), dx.data_ptr()), "clipmi_encoder_bwd")
-    else:
-        for hi, lo in chunks:
-            _lib.check(lib.clipmi_encoder_bwd_layers(s, ctypes.byref(d), dx.data_ptr(), hi, lo),
-                       "clipmi_encoder_bwd_layers")
-    torch.cuda.synchronize()
-    out = x_out.float() if cls else x_out.view(B, N, D)[:, 0].float()
-    return out, dx.view(B, N, D).float(), {f"{l}.{n}": g for l in range(L) for n, g in grads[l].items()}
+    """The non-causal engine, full or in its cls_last mode: (output at the CLS row, dx [B, N, D], gradients)."""
+    return run("cls_last" if cls else "full", dtype, r32, B, N, L, weights, x0, dy0, grad_fill=grad_fill,
+               chunks=chunks)
 
 
 def reference(weights, x0, dy0, xdt, dtype, B, N):
@@ -270,24 +201,6 @@ def reference(weights, x0, dy0, xdt, dtype, B, N):
     out.backward(dy0.to(dtype).double())
     zero = lambda t: torch.zeros_like(t) if t.grad is None else t.grad  # noqa: E731
     return out.detach(), x.grad, {f"{l}.{n}": zero(t) for l, w in enumerate(ws) for n, t in w.items()}
-
-
-def rel_err(got, ref, group_max):
-    scale = max(float(ref.abs().max()), 0.05 * group_max, 1e-6)
-    return float((got.double() - ref).abs().nan_to_num(1e30).max()) / scale
-
-
-def errors(res, ref):
-    out, dx, grads = res
-    rout, rdx, rgrads = ref
-    gmax = max(float(g.abs().max()) for g in rgrads.values())
-    worst = max((rel_err(grads[n], rgrads[n], gmax), n) for n in rgrads)
-    return rel_err(out, rout, float(rout.abs().max())), rel_err(dx, rdx, float(rdx.abs().max())), worst
-
-
-def inputs(B, N, seed=0):
-    g = torch.Generator().manual_seed(1000 * B + N + seed)
-    return torch.randn(B, N, D, generator=g).cuda(), torch.randn(B, D, generator=g).cuda()
 
 
 @pytest.mark.parametrize("B", [1, 3, 33, 300])

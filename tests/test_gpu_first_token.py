@@ -9,98 +9,24 @@ of test_gradients_match_reference (max error over max(|ref| of the tensor, 5 % o
 engines sum the same K products per output, the first-token one in a different tile order.  Three figures are
 compared, as that test forms them: the output at row 0, dx at row 0 (each its own group) and the worst gradient
 tensor of the gradient group.  Measured figures (MI355X) are recorded in DESIGN.md."""
-import ctypes
-import types
-
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from clipmi import CLIPWithAdapters, _lib, synth  # noqa: E402
-from clipmi import kernels as K  # noqa: E402
-from clipmi import towers as T  # noqa: E402
+from engine_harness import D, EPS, MODES, errors, inputs, make_mask, make_weights  # noqa: E402
+from engine_harness import run_engine as run  # noqa: E402
 
-D, H, F, L = 128, 2, 512, 2
-EPS = 1e-5
-TCFG = types.SimpleNamespace(hidden_size=D, intermediate_size=F, num_attention_heads=H, num_hidden_layers=L,
-                             layer_norm_eps=EPS)
-SHAPES = {"ln1_w": (D,), "ln1_b": (D,), "qkv_w": (3 * D, D), "qkv_b": (3 * D,), "out_w": (D, D), "out_b": (D,),
-          "ln2_w": (D,), "ln2_b": (D,), "fc1_w": (F, D), "fc1_b": (F,), "fc2_w": (D, F), "fc2_b": (D,)}
-MODES = {"fp32": (torch.float32, False), "bf16": (torch.bfloat16, False), "bf16_resid32": (torch.bfloat16, True)}
+from clipmi import CLIPWithAdapters, synth  # noqa: E402
 
-
-def make_weights(seed, dtype):
-    """[L] dicts of weights in the engine's dtype (both engines and the fp64 reference read these values)."""
-    g = torch.Generator().manual_seed(seed)
-    out = []
-    for _ in range(L):
-        w = {}
-        for n, shp in SHAPES.items():
-            t = torch.randn(shp, generator=g)
-            if n in ("ln1_w", "ln2_w"):
-                t = 1.0 + 0.1 * t
-            elif n.endswith("_w"):
-                t = t / shp[1] ** 0.5
-            else:
-                t = 0.1 * t
-            w[n] = t.to(dtype).cuda().contiguous()
-        out.append(w)
-    return out
-
-
-def make_mask(kind, B, N):
-    if kind == "null":
-        return None
-    m = torch.ones(B, N, dtype=torch.int64)
-    if kind == "key0":  # token 0's own key padded for every third caption (B = 1: for the only one)
-        m[::3, 0] = 0
-    return m.cuda()
+L = 2
 
 
 def run_engine(first, dtype, r32, B, N, weights, mask, x0, dy0, grad_fill=None):
-    """One forward + backward of the native engine.  x0 [B, N, D] fp32, dy0 [B, D]: the upstream gradient at
-    token 0 (zero elsewhere).  Returns (output at row 0, dx at row 0, {layer.name: gradient}), fp32 on the device;
-    grad_fill: the gradient slots' initial content (default zeros)."""
-    dev = x0.device
-    xdt = torch.float32 if r32 else dtype
-    R = B if first else B * N
-    enc = T.Encoder(None, "text_model", TCFG, causal=True)
-    buf, acts = enc.alloc(B, N, dtype, dev, True, resid32=r32, first_token=first)
-    x_in = (x0[:, 0] if first else x0.reshape(R, D)).to(xdt).contiguous()
-    acts[0].x_in = x_in.data_ptr()
-    wt, gt = (T.LayerW * L)(), (T.LayerG * L)()
-    grads = []
-    for l in range(L):
-        gl = {}
-        for n, shp in SHAPES.items():
-            setattr(wt[l], n, weights[l][n].data_ptr())
-            gl[n] = (torch.zeros(shp, dtype=torch.float32, device=dev) if grad_fill is None
-                     else grad_fill[f"{l}.{n}"].clone())
-            setattr(gt[l], n, gl[n].data_ptr())
-        grads.append(gl)
-    x_out = torch.empty(R, D, dtype=xdt, device=dev)
-    d = T.EncoderDesc()
-    d.dtype, d.B, d.N, d.D, d.F, d.H, d.L, d.eps, d.causal = T.dcode(dtype), B, N, D, F, H, L, EPS, 1
-    d.attention_mask = T.P_(mask)
-    d.layers, d.grads, d.act, d.x_out = wt, gt, acts, x_out.data_ptr()
-    d.resid_f32, d.first_token = int(r32), int(first)
-    s = K.stream()
-    lib = _lib.lib()
-    _lib.check(lib.clipmi_encoder_fwd(s, ctypes.byref(d)), "clipmi_encoder_fwd")
-    ws = torch.empty(max(int(lib.clipmi_encoder_bwd_ws(ctypes.byref(d))), 16), dtype=torch.uint8, device=dev)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    if first:
-        dx = dy0.to(dtype).clone()  # the backward overwrites dx in place
-    else:
-        dx = torch.zeros(B, N, D, dtype=dtype, device=dev)
-        dx[:, 0] = dy0.to(dtype)
-        dx = dx.reshape(R, D)
-    _lib.check(lib.clipmi_encoder_bwd(s, ctypes.byref(d), dx.data_ptr()), "clipmi_encoder_bwd")
-    torch.cuda.synchronize()
-    row0 = (lambda t: t.float()) if first else (lambda t: t.view(B, N, D)[:, 0].float())
-    return row0(x_out), row0(dx), {f"{l}.{n}": g for l in range(L) for n, g in grads[l].items()}
+    """The causal engine, full or in its first_token mode: (output at row 0, dx at row 0, gradients)."""
+    return run("first_token" if first else "full", dtype, r32, B, N, L, weights, x0, dy0, causal=True, mask=mask,
+               grad_fill=grad_fill, row0=True)
 
 
 def reference(weights, mask, x0, dy0, xdt, dtype):
@@ -124,24 +50,6 @@ def reference(weights, mask, x0, dy0, xdt, dtype):
     return h.detach(), x.grad, {f"{l}.{n}": zero(t) for l, w in enumerate(ws) for n, t in w.items()}
 
 
-def rel_err(got, ref, group_max):
-    scale = max(float(ref.abs().max()), 0.05 * group_max, 1e-6)
-    return float((got.double() - ref).abs().max()) / scale
-
-
-def errors(res, ref):
-    out, dx, grads = res
-    rout, rdx, rgrads = ref
-    gmax = max(float(g.abs().max()) for g in rgrads.values())
-    worst = max((rel_err(grads[n], rgrads[n], gmax), n) for n in rgrads)
-    return rel_err(out, rout, float(rout.abs().max())), rel_err(dx, rdx, float(rdx.abs().max())), worst
-
-
-def inputs(B, N, seed=0):
-    g = torch.Generator().manual_seed(1000 * B + N + seed)
-    return torch.randn(B, N, D, generator=g).cuda(), torch.randn(B, D, generator=g).cuda()
-
-
 @pytest.mark.parametrize("mask_kind", ["null", "ones", "key0"])
 @pytest.mark.parametrize("B", [1, 3, 33, 300])
 @pytest.mark.parametrize("N", [1, 7, 77])
@@ -149,7 +57,7 @@ def inputs(B, N, seed=0):
 def test_engine_first_token_matches_full_engine(mode, N, B, mask_kind):
     dtype, r32 = MODES[mode]
     xdt = torch.float32 if r32 else dtype
-    weights = make_weights(7, dtype)
+    weights = make_weights(7, dtype, L)
     mask = make_mask(mask_kind, B, N)
     x0, dy0 = inputs(B, N)
     ref = reference(weights, mask, x0, dy0, xdt, dtype)
@@ -171,7 +79,7 @@ def test_first_token_backward_leaves_qk_slots_and_accumulates(mode, B, mask_kind
     start gives.  after = fl(s + g), so (after - s) - g is within fp32 rounding of the sum: 2^-22 (|s| + |g|)."""
     dtype, r32 = MODES[mode]
     N = 7
-    weights = make_weights(11, dtype)
+    weights = make_weights(11, dtype, L)
     mask = make_mask(mask_kind, B, N)
     x0, dy0 = inputs(B, N, seed=5)
     _, _, g0 = run_engine(True, dtype, r32, B, N, weights, mask, x0, dy0)
@@ -196,7 +104,7 @@ def test_first_token_deferred_reductions_bitwise(mode, B, monkeypatch):
     the default (deferred into the next persistent GEMM) in the first-token mode too."""
     dtype, r32 = MODES[mode]
     N = 7
-    weights = make_weights(13, dtype)
+    weights = make_weights(13, dtype, L)
     mask = make_mask("key0", B, N)
     x0, dy0 = inputs(B, N, seed=9)
     monkeypatch.delenv("CLIPMI_DEFER", raising=False)

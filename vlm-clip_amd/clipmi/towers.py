@@ -4,13 +4,15 @@ Each Function's forward/backward is a short sequence of C-ABI calls (the encoder
 is ONE call per direction, sequenced natively in csrc/engine.cpp).  Parameter
 gradients are written straight into the fp32 gradient arena (``Arena.grad``) and exposed
 as ``p.grad`` views (AccumulateGrad semantics emulated by ``Arena.prepare_grads``), so
-autograd only carries activation gradients between the Functions.
+autograd only carries activation gradients between the Functions.  Each tower has one body
+(VisionTowerFn.run / TextTowerFn.run); its pooled form is a flag of that body and a three-line subclass.
 
 Reference mapping:
   VisionTowerFn  <- CLIPVisionModel.forward ([HF] modeling_clip.py:638-651), last_hidden_state
                     without post_layernorm (model_m.py:116, quirk Q2)
   VisionClsFn    <- the same for CLS pooling (model_m.py:122): the last layer's out-projection and MLP on the CLS rows, [B, 1, D]
   TextTowerFn    <- CLIPTextModel.forward ([HF] :513-559), last_hidden_state after final LN
+  TextFirstTokenFn <- the same for first-token pooling (model_m.py:102): token 0's row alone, [B, 1, D]
   AdapterFn      <- TextAdapter/VisionAdapter.forward (adapter/clip_adapter.py:17-23, 144-150),
                     peclip.TextualAdapter (adapter/peclip.py:13-18) with ln=False
   PoolProjFn     <- [:, 0, :] + text_projection / visual_projection (model_m.py:102-103, 122-123)
@@ -245,21 +247,27 @@ class Encoder:
     def grads(self):
         return self._table(LayerG, self.arena.grad)
 
+    def _shape(self, dtype, B, N, resid32, x3, first_token):
+        """An EncoderDesc with its shape and mode fields set: what clipmi_encoder_act_bytes reads (alloc) and the
+        head of every descriptor handed to the engine (desc)."""
+        t = self.t
+        d = EncoderDesc()
+        d.dtype, d.B, d.N, d.D, d.F, d.H, d.L = dcode(dtype), B, N, t.hidden_size, t.intermediate_size, \
+            t.num_attention_heads, t.num_hidden_layers
+        d.eps, d.causal = t.layer_norm_eps, int(self.causal)
+        d.resid_f32 = int(resid32 and dtype == torch.bfloat16)
+        d.gemm_x3 = int(x3 and dtype == torch.float32)
+        d.first_token = int(first_token)
+        return d
+
     def alloc(self, B, N, dtype, device, train, resid32=False, x3=False, first_token=False):
         """Activation storage: per-layer for training, one shared set for inference.  The byte size of every
         member comes from the engine (clipmi_encoder_act_bytes) for the descriptor's mode: resid32, the residual
         stream (x_in, h) in fp32 (the bf16 mode's fp32 residual stream); x3 (the bf16x3 mode, fp32), ln1 / ln2 /
         act as bf16 split images [R, 3K] and o followed by its image; first_token, B rows (token 0 of each
         sequence) instead of B * N, no o and no lse (include/clipmi.h)."""
-        t = self.t
-        L = t.num_hidden_layers
-        d = EncoderDesc()
-        d.dtype, d.B, d.N, d.D, d.F, d.H, d.L = dcode(dtype), B, N, t.hidden_size, t.intermediate_size, \
-            t.num_attention_heads, L
-        d.causal = int(self.causal)
-        d.resid_f32 = int(resid32 and dtype == torch.bfloat16)
-        d.gemm_x3 = int(x3 and dtype == torch.float32)
-        d.first_token = int(first_token)
+        L = self.t.num_hidden_layers
+        d = self._shape(dtype, B, N, resid32, x3, first_token)
         nb = (c_i64 * len(A_FIELDS))()
         _lib.check(_lib.lib().clipmi_encoder_act_bytes(ctypes.byref(d), nb), "clipmi_encoder_act_bytes")
         al = lambda n: (n + 255) // 256 * 256  # noqa: E731
@@ -311,9 +319,7 @@ class Encoder:
         cls_last: the last layer on the CLS rows only, x_out compact [B, D] (non-causal towers, not with fp8 /
         x3 / a mask; include/clipmi.h)."""
         t = self.t
-        d = EncoderDesc()
-        d.dtype, d.B, d.N, d.D, d.F = dcode(dtype), B, N, t.hidden_size, t.intermediate_size
-        d.resid_f32 = int(resid32 and not fp8)
+        d = self._shape(dtype, B, N, resid32 and not fp8, x3, first_token)
         if fp8:  # bf16 activations, MXFP8 GEMMs (forward only)
             d.dtype = _lib.FP8
             d.layers8 = self.weights8()
@@ -322,22 +328,18 @@ class Encoder:
             s8 = torch.empty(R * (Dh + F) // 32 + 512, dtype=torch.uint8, device=self.arena.device)
             self._scratch8 = (q8, s8)  # alive until the next call; stream order covers reuse
             d.q8, d.s8 = q8.data_ptr(), s8.data_ptr()
-        d.H, d.L, d.eps, d.causal = t.num_attention_heads, t.num_hidden_layers, t.layer_norm_eps, int(self.causal)
         d.attention_mask = P_(mask)
         d.layers = self.weights(wbuf)
         d.grads = grads
         d.act = acts
         d.x_out = x_out
-        d.first_token = int(first_token)
         d.cls_last = int(cls_last)
         if ws is not None:
             d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-        if x3 and dtype == torch.float32:
-            d.gemm_x3 = 1
+        if d.gemm_x3:
             d.x3_keep = _ws(_lib.lib().clipmi_encoder_x3_ws(ctypes.byref(d)), self.arena.device)
             d.x3_ws, d.x3_ws_bytes = d.x3_keep.data_ptr(), d.x3_keep.numel()
         return d
-
 
     def layer_range(self, lo, hi):
         """(offset, numel) of layers lo..hi-1 in the arena: each layer's parameters are one
@@ -548,8 +550,16 @@ class VisionClsFn(VisionTowerFn):
 
 # ------------------------------------------------------------------------------ text
 class TextTowerFn(torch.autograd.Function):
+    """The text tower's last_hidden_state after the final LayerNorm, [B, S, D]."""
+
     @staticmethod
     def forward(ctx, input_ids, attention_mask, anchor, runtime):
+        return TextTowerFn.run(ctx, input_ids, attention_mask, runtime, False)
+
+    @staticmethod
+    def run(ctx, input_ids, attention_mask, runtime, first):
+        """first: token 0 of each sequence alone through the engine's first_token mode, out [B, 1, D]
+        (TextFirstTokenFn)."""
         rt = runtime
         arena, t, dtype = rt.arena, rt.cfg.text_config, rt.dtype
         B, S = input_ids.shape
@@ -559,42 +569,48 @@ class TextTowerFn(torch.autograd.Function):
         dev = input_ids.device
         ids = input_ids.to(torch.int64).contiguous()
         mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous() if attention_mask is not None else None
-        D = t.hidden_size
-        R = B * S
+        D, V = t.hidden_size, t.vocab_size
+        Sr = 1 if first else S  # positions embedded and carried per sequence
+        R = B * Sr
         train = rt.train_tower
         s = K.stream()
         dc = dcode(dtype)
         wbuf = _wbuf(arena, dtype)
-        fp8 = rt.fp8 and not train
+        # the first_token mode has no MXFP8 form (text_first_token) and runs its B rows in exact fp32 under bf16x3
+        fp8 = rt.fp8 and not train and not first
+        x3 = getattr(rt, "x3", False) and not first
         r32 = getattr(rt, "resid32", False) and not fp8  # the fp32 residual stream (bf16 mode)
         xdtype = torch.float32 if r32 else dtype
-        buf, acts = rt.tenc.alloc(B, S, dtype, dev, train, resid32=r32, x3=getattr(rt, "x3", False))
         bad = rt.bad_flag
+        if first:
+            ids, every = ids[:, 0].contiguous(), ids
+            # nn.Embedding's IndexError covers every position: an out-of-vocabulary id past token 0 still sets the flag
+            bad.logical_or_(((every < 0) | (every >= V)).any())
+        buf, acts = rt.tenc.alloc(B, S, dtype, dev, train, resid32=r32, x3=x3, first_token=first)
         ebuf = arena.data if r32 else wbuf  # fp32 token / position embeddings into the fp32 stream
         call("clipmi_text_embed", s, dcode(xdtype), P_(ids), arena.ptr("text_model.embeddings.token_embedding.weight", ebuf),
-             arena.ptr("text_model.embeddings.position_embedding.weight", ebuf), acts[0].x_in, R, S, D, t.vocab_size,
-             P_(bad))
+             arena.ptr("text_model.embeddings.position_embedding.weight", ebuf), acts[0].x_in, R, Sr, D, V, P_(bad))
         xL = torch.empty(R, D, dtype=xdtype, device=dev)
-        d = rt.tenc.desc(dtype, B, S, wbuf, acts, xL.data_ptr(), mask, fp8=fp8, resid32=r32,
-                         x3=getattr(rt, "x3", False))
+        d = rt.tenc.desc(dtype, B, S, wbuf, acts, xL.data_ptr(), mask, fp8=fp8, resid32=r32, x3=x3, first_token=first)
         _lib.check(_lib.lib().clipmi_encoder_fwd(s, ctypes.byref(d)), "clipmi_encoder_fwd")
         del d
-        out = torch.empty(B, S, D, dtype=dtype, device=dev)
+        out = torch.empty(B, Sr, D, dtype=dtype, device=dev)
         stats = torch.empty(2, R, dtype=torch.float32, device=dev)
         call("clipmi_layernorm_fwd2", s, dcode(xdtype), dc, P_(xL), D, P_(out), D,
              arena.ptr("text_model.final_layer_norm.weight", wbuf), arena.ptr("text_model.final_layer_norm.bias", wbuf),
              P_(stats[0]), P_(stats[1]), R, D, t.layer_norm_eps, None, None, 0)
         if train:
             ctx.rt, ctx.B, ctx.S, ctx.buf, ctx.acts = rt, B, S, buf, acts
-            ctx.ids, ctx.mask, ctx.xL, ctx.stats, ctx.r32 = ids, mask, xL, stats, r32
+            ctx.ids, ctx.mask, ctx.xL, ctx.stats, ctx.r32, ctx.first = ids, mask, xL, stats, r32, first
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        rt = ctx.rt
+        rt, first = ctx.rt, ctx.first
         arena, t, dtype = rt.arena, rt.cfg.text_config, rt.dtype
         B, S, D = ctx.B, ctx.S, t.hidden_size
-        R = B * S
+        Sr = 1 if first else S
+        R = B * Sr
         dev = dout.device
         s = K.stream()
         dc = dcode(dtype)
@@ -609,7 +625,7 @@ class TextTowerFn(torch.autograd.Function):
              arena.ptr("text_model.final_layer_norm.weight", g), arena.ptr("text_model.final_layer_norm.bias", g), 1,
              P_(lws), lws.numel(), R, D)
         d = rt.tenc.desc(dtype, B, S, wbuf, ctx.acts, None, ctx.mask, grads=rt.tenc.grads(), resid32=ctx.r32,
-                         x3=getattr(rt, "x3", False))
+                         x3=getattr(rt, "x3", False) and not first, first_token=first)
         ws = _ws(_lib.lib().clipmi_encoder_bwd_ws(ctypes.byref(d)), dev)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         hook = _grad_hook(rt)
@@ -619,7 +635,7 @@ class TextTowerFn(torch.autograd.Function):
         ews = _ws(_lib.lib().clipmi_text_embed_bwd_ws(R, V), dev)
         call("clipmi_text_embed_bwd", s, dc, P_(ctx.ids), P_(dx), R, D, V,
              arena.ptr("text_model.embeddings.token_embedding.weight", g), 1, P_(ews), ews.numel())
-        call("clipmi_period_sum", s, dc, P_(dx), D, B, S, S, D,
+        call("clipmi_period_sum", s, dc, P_(dx), D, B, Sr, Sr, D,  # first: position 0's row alone
              arena.ptr("text_model.embeddings.position_embedding.weight", g), 1)
         if hook is not None:  # token + position embeddings: the arena's first block
             hook(arena, 0, arena.offsets["text_model.encoder.layers.0.layer_norm1.weight"][0])
@@ -633,7 +649,7 @@ def text_first_token(rt):
     return os.environ.get("CLIPMI_TEXT_FIRST_TOKEN", "1") != "0" and not (rt.fp8 and not rt.train_tower)
 
 
-class TextFirstTokenFn(torch.autograd.Function):
+class TextFirstTokenFn(TextTowerFn):
     """TextTowerFn for first-token pooling (model_m.py:102, quirk Q1): the text tower is causal, so token 0
     attends only to itself in every layer and the other tokens never reach the pooled feature or any gradient.
     Embeds ids[:, 0] at position 0, runs the engine's first_token mode on B rows (include/clipmi.h) and the
@@ -644,79 +660,7 @@ class TextFirstTokenFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input_ids, attention_mask, anchor, runtime):
-        rt = runtime
-        arena, t, dtype = rt.arena, rt.cfg.text_config, rt.dtype
-        B, S = input_ids.shape
-        if S > t.max_position_embeddings:
-            raise ValueError(f"Sequence length must be less than max_position_embeddings (got `sequence length`: "
-                             f"{S} and max_position_embeddings: {t.max_position_embeddings}")
-        dev = input_ids.device
-        ids = input_ids.to(torch.int64)
-        mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous() if attention_mask is not None else None
-        D, V = t.hidden_size, t.vocab_size
-        train = rt.train_tower
-        s = K.stream()
-        dc = dcode(dtype)
-        wbuf = _wbuf(arena, dtype)
-        r32 = getattr(rt, "resid32", False)  # the fp32 residual stream (bf16 mode)
-        xdtype = torch.float32 if r32 else dtype
-        ids0 = ids[:, 0].contiguous()
-        bad = rt.bad_flag
-        # nn.Embedding's IndexError covers every position: an out-of-vocabulary id past token 0 still sets the flag
-        bad.logical_or_(((ids < 0) | (ids >= V)).any())
-        buf, acts = rt.tenc.alloc(B, S, dtype, dev, train, resid32=r32, first_token=True)
-        ebuf = arena.data if r32 else wbuf  # fp32 token / position embeddings into the fp32 stream
-        call("clipmi_text_embed", s, dcode(xdtype), P_(ids0), arena.ptr("text_model.embeddings.token_embedding.weight", ebuf),
-             arena.ptr("text_model.embeddings.position_embedding.weight", ebuf), acts[0].x_in, B, 1, D, V, P_(bad))
-        xL = torch.empty(B, D, dtype=xdtype, device=dev)
-        d = rt.tenc.desc(dtype, B, S, wbuf, acts, xL.data_ptr(), mask, resid32=r32, first_token=True)
-        _lib.check(_lib.lib().clipmi_encoder_fwd(s, ctypes.byref(d)), "clipmi_encoder_fwd")
-        del d
-        out = torch.empty(B, 1, D, dtype=dtype, device=dev)
-        stats = torch.empty(2, B, dtype=torch.float32, device=dev)
-        call("clipmi_layernorm_fwd2", s, dcode(xdtype), dc, P_(xL), D, P_(out), D,
-             arena.ptr("text_model.final_layer_norm.weight", wbuf), arena.ptr("text_model.final_layer_norm.bias", wbuf),
-             P_(stats[0]), P_(stats[1]), B, D, t.layer_norm_eps, None, None, 0)
-        if train:
-            ctx.rt, ctx.B, ctx.S, ctx.buf, ctx.acts = rt, B, S, buf, acts
-            ctx.ids0, ctx.mask, ctx.xL, ctx.stats, ctx.r32 = ids0, mask, xL, stats, r32
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        rt = ctx.rt
-        arena, t, dtype = rt.arena, rt.cfg.text_config, rt.dtype
-        B, S, D = ctx.B, ctx.S, t.hidden_size
-        dev = dout.device
-        s = K.stream()
-        dc = dcode(dtype)
-        arena.prepare_grads()
-        wbuf = _wbuf(arena, dtype)
-        g = arena.grad
-        dy = dout.to(dtype).contiguous()
-        dx = torch.empty(B, D, dtype=dtype, device=dev)
-        lws = _ws(_lib.lib().clipmi_layernorm_bwd_ws(B, D), dev)
-        call("clipmi_layernorm_bwd2", s, dcode(ctx.xL.dtype), dc, P_(dy), D, P_(ctx.xL), D, P_(ctx.stats[0]),
-             P_(ctx.stats[1]), arena.ptr("text_model.final_layer_norm.weight", wbuf), P_(dx), D, None, 0,
-             arena.ptr("text_model.final_layer_norm.weight", g), arena.ptr("text_model.final_layer_norm.bias", g), 1,
-             P_(lws), lws.numel(), B, D)
-        d = rt.tenc.desc(dtype, B, S, wbuf, ctx.acts, None, ctx.mask, grads=rt.tenc.grads(), resid32=ctx.r32,
-                         first_token=True)
-        ws = _ws(_lib.lib().clipmi_encoder_bwd_ws(ctypes.byref(d)), dev)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-        hook = _grad_hook(rt)
-        rt.tenc.backward(s, d, dx.data_ptr(), hook)
-        del d, ws
-        V = t.vocab_size
-        ews = _ws(_lib.lib().clipmi_text_embed_bwd_ws(B, V), dev)
-        call("clipmi_text_embed_bwd", s, dc, P_(ctx.ids0), P_(dx), B, D, V,
-             arena.ptr("text_model.embeddings.token_embedding.weight", g), 1, P_(ews), ews.numel())
-        call("clipmi_period_sum", s, dc, P_(dx), D, B, 1, 1, D,  # position 0's row alone
-             arena.ptr("text_model.embeddings.position_embedding.weight", g), 1)
-        if hook is not None:  # token + position embeddings: the arena's first block
-            hook(arena, 0, arena.offsets["text_model.encoder.layers.0.layer_norm1.weight"][0])
-        ctx.buf = ctx.acts = ctx.xL = ctx.stats = None  # released with backward (see VisionTowerFn)
-        return None, None, None, None
+        return TextTowerFn.run(ctx, input_ids, attention_mask, runtime, True)
 
 
 # ------------------------------------------------------------------------------ adapter

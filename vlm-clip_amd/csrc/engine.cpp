@@ -15,12 +15,15 @@
 // column sums for biases, and LN backward with the residual gradient fused.
 // Activation buffers are caller-owned (per layer for training; one shared set for
 // inference), so the engine holds no state and allocates nothing.
-// first_token (causal encoders pooled at token 0, model_m.py:102): token 0 attends only to
-// itself, so the engine runs that row alone -- B compact rows, qkv reduced to the V projection,
-// o = V (no q, k, softmax or attention launch), the rest as above; see include/clipmi.h.
+// The bf16 / fp32 path has one layer body per direction, run on a schedule of three numbers (include/clipmi.h):
+//   R    rows of LN1, qkv and the attention: B * N, or B with first_token
+//   Rm   rows of the out-projection, LN2, fc1 and fc2: R, or B in the last layer with cls_last
+//   ldt  leading dimension with which the out-projection reads o and the residual x_in: D, or N * D in that layer
+// first_token (causal encoders pooled at token 0, model_m.py:102): token 0 attends only to itself, so R = B compact
+// rows, qkv reduced to the V projection and o = V (no q, k, softmax or attention launch).
 // cls_last (the vision tower pooled at CLS without a post-LayerNorm, model_m.py:116-122): only row 0 of the last
-// layer's output is read, so that layer runs as usual through the attention (every row is a key and a value) and its
-// out-projection and MLP on the B CLS rows; see include/clipmi.h.
+// layer's output is read, so that layer runs through the attention on every row (each is a key and a value) and
+// from the out-projection on over the B CLS rows, read in place with ldt = N * D.
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
@@ -36,8 +39,6 @@ int clipmi_layernorm_bwd2(void*, int, int, const void*, int64_t, const void*, in
                           const void*, void*, int64_t, const void*, int64_t, float*, float*, int, void*, int64_t, int,
                           int);
 int64_t clipmi_layernorm_bwd_ws(int R, int D);
-int clipmi_layernorm_bwd(void*, int, const void*, int64_t, const void*, int64_t, const float*, const float*, const void*,
-                         void*, int64_t, const void*, int64_t, float*, float*, int, void*, int64_t, int, int);
 int64_t clipmi_colsum_ws(int R, int N);
 int clipmi_colsum(void*, int, const void*, int64_t, int, int, float*, int, void*, int64_t);
 int clipmi_attention_fwd(void*, int, const void*, void*, float*, const int64_t*, int, int, int, int, int);
@@ -59,10 +60,11 @@ int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 // rows the engine works on: every token, or token 0 of each sequence alone (first_token, clipmi.h)
 int64_t rows(const clipmi_encoder_desc* d) { return d->first_token ? (int64_t)d->B : (int64_t)d->B * d->N; }
 
-int gemm(void* s, int dt, int M, int N, int K, const void* A, int64_t lda, bool akm, const void* B, int64_t ldb,
-         bool bkm, void* C, int64_t ldc, int c_dt, int flags, const void* bias = nullptr, const void* res = nullptr,
-         int64_t ldr = 0, void* aux = nullptr, int64_t ldaux = 0, int split = 1, void* ws = nullptr,
-         int64_t ws_bytes = 0, float* bias_grad = nullptr) {
+// what every GEMM of the engine sets: shapes, operands, alpha = 1, flags, the operand / result / bias dtypes; no
+// split.  The helpers below add their extras (split-K, bias gradient, MXFP8 scales)
+clipmi_gemm_desc gemm_desc(int M, int N, int K, const void* A, int64_t lda, bool akm, const void* B, int64_t ldb,
+                           bool bkm, void* C, int64_t ldc, int flags, const void* bias, const void* res, int64_t ldr,
+                           void* aux, int64_t ldaux, int ab_dt, int c_dt, int bias_dt) {
   clipmi_gemm_desc d;
   memset(&d, 0, sizeof(d));
   d.M = M; d.N = N; d.K = K;
@@ -71,7 +73,16 @@ int gemm(void* s, int dt, int M, int N, int K, const void* A, int64_t lda, bool 
   d.C = C; d.ldc = ldc;
   d.bias = bias; d.residual = res; d.ldr = ldr; d.aux = aux; d.ldaux = ldaux;
   d.alpha = 1.f; d.flags = flags;
-  d.ab_dtype = dt; d.c_dtype = c_dt; d.bias_dtype = dt;
+  d.ab_dtype = ab_dt; d.c_dtype = c_dt; d.bias_dtype = bias_dt;
+  d.split_k = 1;
+  return d;
+}
+
+int gemm(void* s, int dt, int M, int N, int K, const void* A, int64_t lda, bool akm, const void* B, int64_t ldb,
+         bool bkm, void* C, int64_t ldc, int c_dt, int flags, const void* bias = nullptr, const void* res = nullptr,
+         int64_t ldr = 0, void* aux = nullptr, int64_t ldaux = 0, int split = 1, void* ws = nullptr,
+         int64_t ws_bytes = 0, float* bias_grad = nullptr) {
+  clipmi_gemm_desc d = gemm_desc(M, N, K, A, lda, akm, B, ldb, bkm, C, ldc, flags, bias, res, ldr, aux, ldaux, dt, c_dt, dt);
   d.split_k = split; d.workspace = ws; d.workspace_bytes = ws_bytes;
   d.bias_grad = bias_grad;
   return clipmi_gemm(s, &d);
@@ -176,15 +187,8 @@ void* x3_o3(const clipmi_layer_act& a, int64_t R, int D) { return (char*)a.o + a
 int x3_gemm(void* s, int M, int N, int K3, const void* A, int64_t lda, bool akm, const void* B, int64_t ldb, bool bkm,
             void* C, int64_t ldc, int flags, const void* bias = nullptr, const void* res = nullptr, int64_t ldr = 0,
             void* aux = nullptr, int64_t ldaux = 0, int split = 1, void* ws = nullptr, int64_t ws_bytes = 0) {
-  clipmi_gemm_desc g;
-  memset(&g, 0, sizeof(g));
-  g.M = M; g.N = N; g.K = K3;
-  g.A = A; g.lda = lda; g.a_kmajor = akm;
-  g.B = B; g.ldb = ldb; g.b_kmajor = bkm;
-  g.C = C; g.ldc = ldc;
-  g.bias = bias; g.residual = res; g.ldr = ldr; g.aux = aux; g.ldaux = ldaux;
-  g.alpha = 1.f; g.flags = flags;
-  g.ab_dtype = CLIPMI_BF16; g.c_dtype = CLIPMI_F32; g.bias_dtype = CLIPMI_F32;
+  clipmi_gemm_desc g = gemm_desc(M, N, K3, A, lda, akm, B, ldb, bkm, C, ldc, flags, bias, res, ldr, aux, ldaux,
+                                 CLIPMI_BF16, CLIPMI_F32, CLIPMI_F32);
   g.split_k = split; g.workspace = ws; g.workspace_bytes = ws_bytes;
   return clipmi_gemm(s, &g);
 }
@@ -193,16 +197,8 @@ int x3_gemm(void* s, int M, int N, int K3, const void* A, int64_t lda, bool akm,
 int x3_gemm_img(void* s, int M, int N, int K3, const void* A, int64_t lda, const void* B, int64_t ldb, bool bkm,
                 void* C3, int pattern, int flags, const void* bias, void* aux, int64_t ldaux, float* colsum, void* ws,
                 int64_t ws_bytes) {
-  clipmi_gemm_desc g;
-  memset(&g, 0, sizeof(g));
-  g.M = M; g.N = N; g.K = K3;
-  g.A = A; g.lda = lda; g.a_kmajor = 1;
-  g.B = B; g.ldb = ldb; g.b_kmajor = bkm;
-  g.C = C3; g.ldc = 3 * (int64_t)N;
-  g.bias = bias; g.aux = aux; g.ldaux = ldaux;
-  g.alpha = 1.f; g.flags = flags;
-  g.ab_dtype = CLIPMI_BF16; g.c_dtype = CLIPMI_F32; g.bias_dtype = CLIPMI_F32;
-  g.split_k = 1;
+  clipmi_gemm_desc g = gemm_desc(M, N, K3, A, lda, true, B, ldb, bkm, C3, 3 * (int64_t)N, flags, bias, nullptr, 0, aux,
+                                 ldaux, CLIPMI_BF16, CLIPMI_F32, CLIPMI_F32);
   return clipmi_gemm_x3out(s, &g, pattern, colsum, 1, ws, ws_bytes);
 }
 // C[R][N] = epi(X3 W^T): X3 the pattern-0 image [R][3K] of the forward activation, W fp32 [N][K]
@@ -224,6 +220,25 @@ struct WsPlan {
   int64_t g2, dln, dbig, split, colsum, ln, total;
 };
 
+// The weight-gradient GEMMs of the backward loop, [M x N] summed over K tokens, in the order of its wgrad calls:
+// fc2, fc1 and the out-projection over Rm tokens (R, and the B CLS rows of cls_last's last layer; see the header),
+// then qkv over R (first_token: V alone, sized as qkv here).
+struct WgradShape {
+  int M, N, K;
+};
+int wgrad_shapes(const clipmi_encoder_desc* d, WgradShape out[7]) {
+  const int R = (int)rows(d), D = d->D, F = d->F;
+  int n = 0;
+  for (int K : {R, d->B}) {
+    out[n++] = {D, F, K};
+    out[n++] = {F, D, K};
+    out[n++] = {D, D, K};
+    if (!d->cls_last) break;
+  }
+  out[n++] = {3 * D, D, R};
+  return n;
+}
+
 WsPlan plan(const clipmi_encoder_desc* d) {
   const int64_t R = rows(d);
   const size_t es = esize(d->dtype);
@@ -234,17 +249,12 @@ WsPlan plan(const clipmi_encoder_desc* d) {
   p.dbig = p.dln + align256(R * d->D * es);
   p.split = p.dbig + align256(R * big * es);
   int64_t sp = 0;
-  const int shapes[4][2] = {{d->F, d->D}, {d->D, d->F}, {d->D, d->D}, {3 * d->D, d->D}};
-  for (auto& sh : shapes) {
-    const int s = (d->gemm_x3 && d->dtype == CLIPMI_F32) ? 1 : wgrad_splits(sh[0], sh[1], (int)R, d->dtype);
-    if (s > 1) sp = std::max<int64_t>(sp, (int64_t)s * sh[0] * (sh[1] + 1) * 4);  // slabs + bias partials
-  }
-  if (d->cls_last) {  // the last layer's out-projection / MLP weight gradients sum over the B CLS rows
-    const int cshapes[3][3] = {{d->D, d->D, d->B}, {d->F, d->D, d->B}, {d->D, d->F, d->B}};
-    for (auto& sh : cshapes) {
-      const int s = wgrad_splits(sh[0], sh[1], sh[2], d->dtype);
-      if (s > 1) sp = std::max<int64_t>(sp, (int64_t)s * sh[0] * (sh[1] + 1) * 4);
-    }
+  WgradShape shapes[7];
+  const int n = wgrad_shapes(d, shapes);
+  for (int i = 0; i < n; ++i) {
+    const WgradShape& sh = shapes[i];
+    const int s = x3_mode(d) ? 1 : wgrad_splits(sh.M, sh.N, sh.K, d->dtype);
+    if (s > 1) sp = std::max<int64_t>(sp, (int64_t)s * sh.M * (sh.N + 1) * 4);  // slabs + bias partials
   }
   // bf16: two slab regions used alternately, so a weight gradient's split-K sum can be deferred into the
   // next persistent GEMM while the following weight gradient writes its own slabs (DeferredReduce)
@@ -259,18 +269,10 @@ WsPlan plan(const clipmi_encoder_desc* d) {
 // (c_scale != NULL: C is written as MXFP8 too, scales [M, N/32] in c_scale)
 int gemm8q(void* s, int M, int N, int K, const void* q8, const void* s8, const void* Wq, const void* Ws, void* C,
            int64_t ldc, int flags, const void* bias, const void* res, int64_t ldr, uint8_t* c_scale = nullptr) {
-  clipmi_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.M = M; d.N = N; d.K = K;
-  d.A = q8; d.lda = K; d.a_kmajor = 1;
-  d.B = Wq; d.ldb = K; d.b_kmajor = 1;
+  clipmi_gemm_desc d = gemm_desc(M, N, K, q8, K, true, Wq, K, true, C, ldc, flags, bias, res, ldr, nullptr, 0, CLIPMI_FP8,
+                                 c_scale ? CLIPMI_FP8 : CLIPMI_BF16, CLIPMI_BF16);
   d.a_scale = (const uint8_t*)s8; d.b_scale = (const uint8_t*)Ws;
-  d.C = C; d.ldc = ldc;
-  d.bias = bias; d.residual = res; d.ldr = ldr;
-  d.alpha = 1.f; d.flags = flags;
-  d.ab_dtype = CLIPMI_FP8; d.c_dtype = c_scale ? CLIPMI_FP8 : CLIPMI_BF16; d.bias_dtype = CLIPMI_BF16;
   d.c_scale = c_scale;
-  d.split_k = 1;
   return clipmi_gemm(s, &d);
 }
 // the same with A [M, K] bf16 quantised into the q8/s8 scratch first
@@ -534,25 +536,13 @@ extern "C" int clipmi_encoder_fwd(void* s, const clipmi_encoder_desc* d) {
     const clipmi_layer_w& w = d->layers[l];
     const clipmi_layer_act& a = d->act[l];
     void* x_out = (l + 1 < d->L) ? d->act[l + 1].x_in : d->x_out;
+    // the layer's schedule (header): only the CLS rows of a tail layer's output are read, so from the out-projection
+    // on it runs on those B rows, read in place; the attention before it needs every row as a key and a value
+    const bool tail = d->cls_last && l == d->L - 1;
+    const int Rm = tail ? d->B : R;
+    const int64_t ldt = tail ? (int64_t)d->N * D : D;
     CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.x_in, D, a.ln1, D, w.ln1_w, w.ln1_b, a.mean1, a.rstd1, R, D, d->eps,
                                      nullptr, nullptr, 0));
-    if (d->cls_last && l == d->L - 1) {  // only the CLS rows of this layer's output are read (clipmi.h cls_last):
-      // the layer runs as usual through the attention (every row is a key and a value, and the same kernels keep the
-      // CLS row's bits), then on the B CLS rows, read in place with a leading dimension of N * D
-      const int B = d->B;
-      const int64_t ldcls = (int64_t)d->N * D;
-      CLIPMI_TRY(gemm(s, dt, R, 3 * D, D, a.ln1, D, true, w.qkv_w, D, true, a.qkv, 3 * D, dt, CLIPMI_EPI_BIAS, w.qkv_b));
-      CLIPMI_TRY(clipmi_attention_fwd(s, dt, a.qkv, a.o, a.lse, nullptr, 0, B, d->H, d->N, D));
-      CLIPMI_TRY(gemm(s, dt, B, D, D, a.o, ldcls, true, w.out_w, D, true, a.h, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
-                      w.out_b, a.x_in, ldcls));
-      CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.h, D, a.ln2, D, w.ln2_w, w.ln2_b, a.mean2, a.rstd2, B, D, d->eps,
-                                       nullptr, nullptr, 0));
-      const int f1 = CLIPMI_EPI_BIAS | CLIPMI_EPI_QGELU | (a.pre ? CLIPMI_EPI_STORE_DACT : 0);
-      CLIPMI_TRY(gemm(s, dt, B, F, D, a.ln2, D, true, w.fc1_w, D, true, a.act, F, dt, f1, w.fc1_b, nullptr, 0, a.pre, F));
-      CLIPMI_TRY(gemm(s, dt, B, D, F, a.act, F, true, w.fc2_w, F, true, x_out, D, xdt,
-                      CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID, w.fc2_b, a.h, D));
-      continue;
-    }
     const void* o = a.o;
     if (d->first_token) {  // token 0 sees one key, itself: O = V (0 where that key is padded), no q, k or softmax
       const size_t es = esize(dt);
@@ -564,15 +554,15 @@ extern "C" int clipmi_encoder_fwd(void* s, const clipmi_encoder_desc* d) {
       CLIPMI_TRY(gemm(s, dt, R, 3 * D, D, a.ln1, D, true, w.qkv_w, D, true, a.qkv, 3 * D, dt, CLIPMI_EPI_BIAS, w.qkv_b));
       CLIPMI_TRY(clipmi_attention_fwd(s, dt, a.qkv, a.o, a.lse, d->attention_mask, d->causal, d->B, d->H, d->N, D));
     }
-    CLIPMI_TRY(gemm(s, dt, R, D, D, o, D, true, w.out_w, D, true, a.h, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
-                    w.out_b, a.x_in, D));
-    CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.h, D, a.ln2, D, w.ln2_w, w.ln2_b, a.mean2, a.rstd2, R, D, d->eps,
+    CLIPMI_TRY(gemm(s, dt, Rm, D, D, o, ldt, true, w.out_w, D, true, a.h, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
+                    w.out_b, a.x_in, ldt));
+    CLIPMI_TRY(clipmi_layernorm_fwd2(s, xdt, dt, a.h, D, a.ln2, D, w.ln2_w, w.ln2_b, a.mean2, a.rstd2, Rm, D, d->eps,
                                      nullptr, nullptr, 0));
     // training: a.pre receives quick_gelu'(pre) (computed beside the activation from the fp32
     // pre-activation), so fc2's input gradient below is one product per element
     const int f1 = CLIPMI_EPI_BIAS | CLIPMI_EPI_QGELU | (a.pre ? CLIPMI_EPI_STORE_DACT : 0);
-    CLIPMI_TRY(gemm(s, dt, R, F, D, a.ln2, D, true, w.fc1_w, D, true, a.act, F, dt, f1, w.fc1_b, nullptr, 0, a.pre, F));
-    CLIPMI_TRY(gemm(s, dt, R, D, F, a.act, F, true, w.fc2_w, F, true, x_out, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
+    CLIPMI_TRY(gemm(s, dt, Rm, F, D, a.ln2, D, true, w.fc1_w, D, true, a.act, F, dt, f1, w.fc1_b, nullptr, 0, a.pre, F));
+    CLIPMI_TRY(gemm(s, dt, Rm, D, F, a.act, F, true, w.fc2_w, F, true, x_out, D, xdt, CLIPMI_EPI_BIAS | CLIPMI_EPI_RESID,
                     w.fc2_b, a.h, D));
   }
   return CLIPMI_OK;
@@ -624,7 +614,7 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
   int wg_no = 0;
   // wgrad: C[M,N] += sum_tokens A[t][m] B[t][n]; the bf16 path also fuses the Linear bias
   // gradient (sum_tokens A[t][m]) into the same GEMM, fp32 uses a column-sum pass
-  // (Kt tokens: R, or the B CLS rows of a cls_last layer)
+  // (Kt tokens: R or Rm; wgrad_shapes lists the same calls for plan())
   auto wgrad = [&](int Kt, int M, int N, const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
                    float* bgrad) -> int {
     const int sp = wgrad_splits(M, N, Kt, d->dtype);
@@ -660,42 +650,24 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
     const clipmi_layer_act& a = d->act[l];
     const clipmi_layer_grad& g = d->grads[l];
     CLIPMI_REQUIRE(a.pre, "training forward must save pre-activations");
-    if (d->cls_last && l == d->L - 1) {  // the forward ran this layer's out-projection and MLP for the CLS rows only
-      // (clipmi.h cls_last): dx holds dL/dx_out [B][D] in its head; the MLP and out-projection branches are the full
-      // layer's on B rows, the attention branch the full layer's with d_o zero at every other row
-      const int B = d->B;
-      const int64_t ldcls = (int64_t)d->N * D;
-      CLIPMI_TRY(gemm(s, dt, B, F, D, dx, D, true, w.fc2_w, F, false, dbig, F, dt, CLIPMI_EPI_MUL_AUX, nullptr,
-                      nullptr, 0, a.pre, F));                                            // d_pre
-      CLIPMI_TRY(wgrad(B, D, F, dx, D, a.act, F, g.fc2_w, g.fc2_b));                     // gW2, gb2
-      CLIPMI_TRY(wgrad(B, F, D, dbig, F, a.ln2, D, g.fc1_w, g.fc1_b));                   // gW1, gb1
-      CLIPMI_TRY(gemm(s, dt, B, D, F, dbig, F, true, w.fc1_w, D, false, dln, D, dt, 0)); // d_ln2
-      CLIPMI_TRY(ln_guard());
-      CLIPMI_TRY(clipmi_layernorm_bwd2(s, xdt, dt, dln, D, a.h, D, a.mean2, a.rstd2, w.ln2_w, g2, D, dx, D, g.ln2_w,
-                                       g.ln2_b, 1, wln, ln_bytes, B, D));                // dh [B][D]
-      CLIPMI_TRY(wgrad(B, D, D, g2, D, a.o, ldcls, g.out_w, g.out_b));                   // gWo += dh^T o_cls
-      // d_o [R][D]: dh Wo at the CLS rows, zero elsewhere (those rows' outputs were not read)
-      CLIPMI_HIP(hipMemsetAsync(dln, 0, (size_t)R * D * esize(dt), (hipStream_t)s));
-      CLIPMI_TRY(gemm(s, dt, B, D, D, g2, D, true, w.out_w, D, false, dln, ldcls, dt, 0));
-      CLIPMI_TRY(clipmi_attention_bwd(s, dt, a.qkv, a.o, a.lse, dln, dbig, nullptr, 0, B, d->H, d->N, D));  // d_qkv
-      CLIPMI_TRY(wgrad(R, 3 * D, D, dbig, 3 * D, a.ln1, D, g.qkv_w, g.qkv_b));           // gWqkv += d_qkv^T ln1
-      CLIPMI_TRY(gemm(s, dt, R, D, 3 * D, dbig, 3 * D, true, w.qkv_w, D, false, dln, D, dt, 0));  // d_ln1
-      CLIPMI_TRY(ln_guard());
-      CLIPMI_TRY(clipmi_layernorm_bwd4(s, xdt, dt, dt, dln, D, a.x_in, D, a.mean1, a.rstd1, w.ln1_w, dx, D, g2, D, d->N,
-                                       g.ln1_w, g.ln1_b, 1, wln, ln_bytes, R, D));       // dx_in = [dh at CLS] + LN1'
-      continue;
-    }
+    // the forward's schedule (header): a tail layer ran its out-projection and MLP for the B CLS rows only, and dx
+    // holds dL/dx_out [B][D] in its head
+    const bool tail = d->cls_last && l == d->L - 1;
+    const int Rm = tail ? d->B : R;
+    const int64_t ldt = tail ? (int64_t)d->N * D : D;
     // MLP branch: dx is dL/dy
-    CLIPMI_TRY(gemm(s, dt, R, F, D, dx, D, true, w.fc2_w, F, false, dbig, F, dt, CLIPMI_EPI_MUL_AUX, nullptr, nullptr,
+    CLIPMI_TRY(gemm(s, dt, Rm, F, D, dx, D, true, w.fc2_w, F, false, dbig, F, dt, CLIPMI_EPI_MUL_AUX, nullptr, nullptr,
                     0, a.pre, F));                                          // d_pre = (dx W2) * qgelu'(pre)
-    CLIPMI_TRY(wgrad(R, D, F, dx, D, a.act, F, g.fc2_w, g.fc2_b));            // gW2 += dx^T act, gb2 += sum dx
-    CLIPMI_TRY(wgrad(R, F, D, dbig, F, a.ln2, D, g.fc1_w, g.fc1_b));          // gW1 += d_pre^T ln2
-    CLIPMI_TRY(gemm(s, dt, R, D, F, dbig, F, true, w.fc1_w, D, false, dln, D, dt, 0));  // d_ln2 = d_pre W1
+    CLIPMI_TRY(wgrad(Rm, D, F, dx, D, a.act, F, g.fc2_w, g.fc2_b));           // gW2 += dx^T act, gb2 += sum dx
+    CLIPMI_TRY(wgrad(Rm, F, D, dbig, F, a.ln2, D, g.fc1_w, g.fc1_b));         // gW1 += d_pre^T ln2
+    CLIPMI_TRY(gemm(s, dt, Rm, D, F, dbig, F, true, w.fc1_w, D, false, dln, D, dt, 0));  // d_ln2 = d_pre W1
     CLIPMI_TRY(ln_guard());
-    CLIPMI_TRY(clipmi_layernorm_bwd2(s, xdt, dt, dln, D, a.h, D, a.mean2, a.rstd2, w.ln2_w, g2, D, dx, D, g.ln2_w,
-                                     g.ln2_b, 1, wln, ln_bytes, R, D));   // dh = dx + LN2'(d_ln2)
-    // attention branch: g2 is dL/dh
-    CLIPMI_TRY(gemm(s, dt, R, D, D, g2, D, true, w.out_w, D, false, dln, D, dt, 0));     // d_o = dh Wo
+    CLIPMI_TRY(clipmi_layernorm_bwd4(s, xdt, dt, dt, dln, D, a.h, D, a.mean2, a.rstd2, w.ln2_w, g2, D, dx, D, 0, g.ln2_w,
+                                     g.ln2_b, 1, wln, ln_bytes, Rm, D));  // dh = dx + LN2'(d_ln2)
+    // attention branch: g2 is dL/dh.  d_o = dh Wo; a tail layer's is zero at every row but the CLS rows (the other
+    // rows' outputs were not read)
+    if (tail) CLIPMI_HIP(hipMemsetAsync(dln, 0, (size_t)R * D * esize(dt), (hipStream_t)s));
+    CLIPMI_TRY(gemm(s, dt, Rm, D, D, g2, D, true, w.out_w, D, false, dln, ldt, dt, 0));
     const void* dln1 = dln;
     if (d->first_token) {  // O is V (act[l].qkv, row-selected): dV = d_o with the same select; the q / k slots of
                            // gWqkv / gbqkv are left alone (their gradient is exactly zero)
@@ -706,15 +678,16 @@ extern "C" int clipmi_encoder_bwd_layers(void* s, const clipmi_encoder_desc* d, 
                       dbig, D, dt, 0));                                                   // d_ln1 = dV Wv
       dln1 = dbig;
     } else {
-      CLIPMI_TRY(wgrad(R, D, D, g2, D, a.o, D, g.out_w, g.out_b));                          // gWo += dh^T o
+      CLIPMI_TRY(wgrad(Rm, D, D, g2, D, a.o, ldt, g.out_w, g.out_b));                       // gWo += dh^T o
       CLIPMI_TRY(clipmi_attention_bwd(s, dt, a.qkv, a.o, a.lse, dln, dbig, d->attention_mask, d->causal, d->B, d->H,
                                       d->N, D));                            // d_qkv
       CLIPMI_TRY(wgrad(R, 3 * D, D, dbig, 3 * D, a.ln1, D, g.qkv_w, g.qkv_b));  // gWqkv += d_qkv^T ln1
       CLIPMI_TRY(gemm(s, dt, R, D, 3 * D, dbig, 3 * D, true, w.qkv_w, D, false, dln, D, dt, 0));  // d_ln1
     }
     CLIPMI_TRY(ln_guard());
-    CLIPMI_TRY(clipmi_layernorm_bwd2(s, xdt, dt, dln1, D, a.x_in, D, a.mean1, a.rstd1, w.ln1_w, dx, D, g2, D, g.ln1_w,
-                                     g.ln1_b, 1, wln, ln_bytes, R, D));    // dx_in = dh + LN1'(d_ln1)
+    // dx_in = dh + LN1'(d_ln1); a tail layer's dh is compact, row b added at row b * N alone
+    CLIPMI_TRY(clipmi_layernorm_bwd4(s, xdt, dt, dt, dln1, D, a.x_in, D, a.mean1, a.rstd1, w.ln1_w, dx, D, g2, D,
+                                     tail ? d->N : 0, g.ln1_w, g.ln1_b, 1, wln, ln_bytes, R, D));
   }
   if (pend.kind != 0) CLIPMI_TRY(launch_deferred((hipStream_t)s, pend));  // this call's gradients are final
   return CLIPMI_OK;
