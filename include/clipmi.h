@@ -34,7 +34,8 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
 /* 2: clipmi_encoder_desc gained first_token (appended); clipmi_encoder_act_bytes
  * 3: evaluation entry points (clipmi_rank_pick, clipmi_rank_count, clipmi_classify_accumulate)
  * 4: clipmi_topk_merge
- * 5: clipmi_encoder_desc gained cls_last (appended); clipmi_attention_cls_fwd / _bwd, clipmi_layernorm_bwd4 */
+ * 5: clipmi_encoder_desc gained cls_last (appended); clipmi_attention_cls_fwd / _bwd, clipmi_layernorm_bwd4
+ * 6: clipmi_resize_crop_u8 (ragged image batches) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -237,6 +238,29 @@ int clipmi_im2col_u8(void* stream, int dtype, const uint8_t* images, void* X, in
 int64_t clipmi_resize_u8_ws(int B, int Hin, int Win, int Hout, int Wout);
 int clipmi_resize_u8(void* stream, const uint8_t* in, int B, int Hin, int Win, uint8_t* out, int Hout, int Wout,
                      void* ws, int64_t ws_bytes);
+/* Ragged input step (csrc/images.hip; clipmi_version() >= 6): B channels-last RGB uint8 images of different sizes in
+ * one packed device buffer -> out uint8 [B, S, S, 3], which clipmi_im2col_u8 takes with Hin = Win = S.  Item b is
+ * image b ([h, w, 3] at byte `offset`), an integer crop box (x0, y0, cw, ch) inside it (the whole image: 0, 0, w, h)
+ * and flip in {0, 1}.  Semantics: crop, then PIL Image.resize(BICUBIC) of the crop, then the rest; bit-exact with the
+ * same fixed-point scheme as clipmi_resize_u8 (taps clamp at the crop's edges, not the image's; a pass whose size
+ * does not change is the identity).
+ *   mode 0 (processor): the crop's short edge -> S, the long edge -> int(S * long / short); of that image only the
+ *                       centre S x S window (offsets (out - S) / 2, clipmi_im2col_u8's) is computed
+ *   mode 1 (square):    the crop straight to S x S (a random-resized-crop)
+ * flip mirrors the output's columns after the resize (out[y][x] = resized[y][S-1-x]); flipping the source is not
+ * bit-identical (tap ranges truncate asymmetrically).  Downscales up to 32 per axis (129 taps); larger ones, a box
+ * outside its image, an image outside [0, packed_bytes), flip or mode out of range return CLIPMI_ERR_INVALID naming
+ * the item, before any launch.  `items` is host memory: the library validates it, derives the per-image launch
+ * records and uploads those into the workspace on the stream; the kernels read nothing else of the caller's but
+ * the pixels.  Three launches whatever B is.  clipmi_resize_crop_u8_ws returns the workspace bytes (a negative
+ * status on invalid items). */
+typedef struct clipmi_image_item {
+  int64_t offset;
+  int32_t h, w, x0, y0, cw, ch, flip;
+} clipmi_image_item;
+int64_t clipmi_resize_crop_u8_ws(const clipmi_image_item* items, int B, int S, int mode);
+int clipmi_resize_crop_u8(void* stream, const uint8_t* packed, int64_t packed_bytes, const clipmi_image_item* items,
+                          int B, uint8_t* out, int S, int mode, void* ws, int64_t ws_bytes);
 /* pooled token per row: mode 0 first token (model_m.py:102), 1 first EOS (0 when the row has none), 2 argmax id,
  * the first of tied maxima ([HF] :561-581).  gather: out[b] = src[b*S + idx[b]]; scatter: dst[b*S + idx[b]] (+)=
  * src[b], the other rows of dst untouched; idx NULL: token 0.  B = 0 is a no-op. */

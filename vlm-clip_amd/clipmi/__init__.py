@@ -20,12 +20,16 @@ def __getattr__(name):
     if name in ("CLIPAdapterTrainer", "FusedAdamW"):
         from . import trainer
         return getattr(trainer, name)
+    if name in _IMAGES:  # ragged image batches and augmentation on the GPU input step
+        from . import images
+        return getattr(images, name)
     if name in _EVALUATION:  # on-device retrieval ranks and classification metrics
         from . import evaluation
         return getattr(evaluation, name)
     raise AttributeError(name)
 
 
+_IMAGES = ("ImageBatch", "preprocess", "random_resized_crop_boxes", "random_flips", "TrainAugment", "collate")
 _EVALUATION = ("RankResult", "target_ranks", "TopK", "topk", "recall_at_k", "rank_summary", "evaluate_retrieval",
                "ClassificationMeter", "ClassificationResult", "classification_report", "accuracy", "evaluate_model",
                "evaluate_enhanced_model")

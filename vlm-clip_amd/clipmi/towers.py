@@ -30,6 +30,7 @@ from . import _lib
 from . import comm as CM
 from . import kernels as K
 from ._lib import BF16, F32
+from .images import ImageBatch, preprocess
 
 c_vp, c_i64, c_int, c_float = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
 
@@ -400,6 +401,10 @@ class VisionTowerFn(torch.autograd.Function):
         """pooled: the engine's cls_last mode, out [B, 1, D] (VisionClsFn)."""
         rt = runtime
         arena, v, dtype = rt.arena, rt.cfg.vision_config, rt.dtype
+        if isinstance(pixel_values, ImageBatch):  # images of different sizes, crop boxes, flips: one resize call
+            if v.num_channels != 3:
+                raise ValueError("an ImageBatch holds RGB images; the model takes another channel count")
+            pixel_values = preprocess(pixel_values, v.image_size)
         B = pixel_values.shape[0]
         raw = pixel_values.dtype == torch.uint8  # decoded images, channels last: fused input step
         if raw:

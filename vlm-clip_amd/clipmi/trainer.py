@@ -18,6 +18,7 @@ from . import _lib
 from . import comm as CM
 from . import kernels as K
 from . import towers as T
+from .images import ImageBatch
 
 
 def linear_schedule_with_warmup(step, warmup, total):
@@ -233,6 +234,12 @@ class FusedAdamW:
             a.mark_shadow_fresh()
 
 
+def _to_device(batch, device, non_blocking):
+    """The batch's tensors and ImageBatch on the device; other values as they are."""
+    return {k: v.to(device, non_blocking=non_blocking) if isinstance(v, (torch.Tensor, ImageBatch)) else v
+            for k, v in batch.items()}
+
+
 class CLIPAdapterTrainer:
     """trainer.py:11-167.  ``trainable="adapter"`` selects parameters whose name contains
     "adapter" exactly like trainer.py:40-43; ``trainable="requires_grad"`` takes every
@@ -240,8 +247,10 @@ class CLIPAdapterTrainer:
 
     def __init__(self, model, train_dataloader, val_dataloader=None, learning_rate=5e-5, weight_decay=0.01,
                  warmup_steps=0, max_grad_norm=1.0, output_dir="./clip_adapter_checkpoints", *,
-                 trainable="adapter", process_group=None):
+                 trainable="adapter", process_group=None, augment=None):
         self.model = model
+        # ImageBatch -> ImageBatch (clipmi.images.TrainAugment), applied by train_step only; no reference counterpart
+        self.augment = augment
         self.train_dataloader = train_dataloader
         self.val_dataloader = val_dataloader
         self.learning_rate = learning_rate
@@ -276,7 +285,9 @@ class CLIPAdapterTrainer:
     def train_step(self, batch, step, total_steps):
         """One reference step (trainer.py:81-99); returns the loss tensor (no host sync)."""
         device = self.model.clip.arena.device
-        batch = {k: v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+        batch = _to_device(batch, device, True)
+        if self.augment is not None and isinstance(batch.get("pixel_values"), ImageBatch):
+            batch["pixel_values"] = self.augment(batch["pixel_values"])
         outputs = self.model(input_ids=batch.get("input_ids"), attention_mask=batch.get("attention_mask"),
                              pixel_values=batch.get("pixel_values"), return_loss=True)
         loss = outputs["loss"]
@@ -320,7 +331,7 @@ class CLIPAdapterTrainer:
         val_loss = 0.0
         with torch.no_grad():
             for batch in self.val_dataloader:
-                batch = {k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+                batch = _to_device(batch, device, False)
                 outputs = self.model(input_ids=batch.get("input_ids"), attention_mask=batch.get("attention_mask"),
                                      pixel_values=batch.get("pixel_values"), return_loss=True)
                 val_loss += outputs["loss"].item()
