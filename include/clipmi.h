@@ -35,7 +35,8 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
  * 3: evaluation entry points (clipmi_rank_pick, clipmi_rank_count, clipmi_classify_accumulate)
  * 4: clipmi_topk_merge
  * 5: clipmi_encoder_desc gained cls_last (appended); clipmi_attention_cls_fwd / _bwd, clipmi_layernorm_bwd4
- * 6: clipmi_resize_crop_u8 (ragged image batches) */
+ * 6: clipmi_resize_crop_u8 (ragged image batches)
+ * 7: clipmi_contrastive_keyed_* (multi-positive contrastive head), clipmi_row_hash64 */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -466,6 +467,33 @@ int clipmi_contrastive_ce_bwd_chunk(void* stream, const float* S, const float* l
                                     const float* grad_out, int B, int C, int col0, int Bg, int label0, float norm,
                                     float* dS, float* dls_row, int beta);
 int clipmi_sum2(void* stream, const float* a, const float* b, int n, float scale, float* out, int beta);
+
+/* ---- Multi-positive contrastive head (csrc/contrastive_keys.hip), fp32 -------------------------
+ * keys_all int64 [Bg]: one key per pair of the global batch.  Row i (global index label0 + i) of a [B, Bg] score
+ * block has the positives P_i = { j : keys_all[j] == keys_all[label0 + i] }, and
+ *   ce_i = lse_i - winv_i * sum_{j in P_i} logit_ij,  winv_i = 1 / |P_i|
+ *   dlogit_ij = g * norm * (softmax_ij - [j in P_i] winv_i);  dls_row as in clipmi_contrastive_ce_bwd.
+ * With all keys distinct every output is bit for bit that of the clipmi_contrastive_ce_* entry point of the same
+ * form (winv = 1).  Guards: keys_all non-null, 0 <= label0, label0 + B <= Bg, chunk inside [0, Bg); B = 0 returns. */
+int clipmi_contrastive_keyed_fwd(void* stream, const float* S, float* logits, const float* logit_scale,
+                                 const int64_t* keys_all, int B, int Bg, int label0, float* lse, float* ce,
+                                 float* winv);
+int clipmi_contrastive_keyed_bwd(void* stream, const float* logits, const float* lse, const float* winv,
+                                 const float* logit_scale, const float* grad_out, const int64_t* keys_all, int B,
+                                 int Bg, int label0, float norm, float* dS, float* dls_row);
+/* Column-streamed form, as clipmi_contrastive_ce_fwd_chunk / _finish / _bwd_chunk: the running state is
+ * run [B][4] = (max, sum-of-exp, positive-logit sum, positive count as an int32 bit pattern); col0 == 0 initialises
+ * it, a chunk without a positive of a row leaves that row's last two unchanged.  finish writes lse, ce and winv. */
+int clipmi_contrastive_keyed_fwd_chunk(void* stream, const float* S, const float* logit_scale, const int64_t* keys_all,
+                                       int B, int C, int col0, int Bg, int label0, float* run);
+int clipmi_contrastive_keyed_finish(void* stream, const float* run, int B, float* lse, float* ce, float* winv);
+int clipmi_contrastive_keyed_bwd_chunk(void* stream, const float* S, const float* lse, const float* winv,
+                                       const float* logit_scale, const float* grad_out, const int64_t* keys_all, int B,
+                                       int C, int col0, int Bg, int label0, float norm, float* dS, float* dls_row,
+                                       int beta);
+/* out[r] = 64-bit FNV-1a over ids[r][0:N), each token one uint64: h = (h ^ v) * 0x100000001b3 from
+ * 0xcbf29ce484222325 ("same caption" as a key, on the device) */
+int clipmi_row_hash64(void* stream, const int64_t* ids, int B, int N, int64_t* out);
 
 /* ---- Optimizer (trainer.py:95,98; [HF] optimization.py:101-129) ------------------------------ */
 int64_t clipmi_grad_norm_ws(void);

@@ -16,6 +16,8 @@ checkpoint format and error types as the reference; the compute runs on libclipm
   init_seed    seed of the deterministic random init used when no weights file exists
   process_group data-parallel group of the contrastive loss: a torch.distributed group (RCCL
                through torch, or gloo) or a clipmi.comm.Communicator (RCCL issued by libclipmi)
+  forward(..., pair_keys=...)  one integer key per pair: pairs with equal keys are positives of each other in the
+               loss (multi-positive InfoNCE, clipmi.losses); None is the reference's diagonal loss
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ from . import comm as CM
 from . import config as C
 from . import synth
 from . import towers as T
+from .losses import as_pair_keys
 from .modules import AdapterParams, CLIPParams
 
 
@@ -312,8 +315,14 @@ class CLIPWithAdapters(nn.Module):
             self._side = st
         return st
 
-    def forward(self, input_ids=None, attention_mask=None, pixel_values=None, return_loss=True):
-        """model_m.py:127-176."""
+    def forward(self, input_ids=None, attention_mask=None, pixel_values=None, return_loss=True, *, pair_keys=None):
+        """model_m.py:127-176.  pair_keys (extension): one integer key per pair of this rank's batch (an int32 /
+        int64 tensor or a sequence of ints of length B); pairs of the global batch with equal keys are each other's
+        positives in the loss (towers.KeyedContrastiveFn; clipmi.losses builds keys from captions or class names).
+        None: the reference's diagonal loss.  The logits outputs do not depend on it."""
+        keys = None
+        if pair_keys is not None and return_loss and input_ids is not None and pixel_values is not None:
+            keys = as_pair_keys(pair_keys, len(input_ids), self.clip.arena.device)
         if self._overlap_ok(input_ids, attention_mask, pixel_values):
             text_features, image_features = self._both_towers_overlapped(input_ids, attention_mask, pixel_values)
         else:
@@ -324,8 +333,12 @@ class CLIPWithAdapters(nn.Module):
             image_features = self.get_image_features(pixel_values) if pixel_values is not None else None
         if return_loss and text_features is not None and image_features is not None:
             group = self.process_group
-            loss, t, i, lpt, lpi = T.ContrastiveFn.apply(text_features, image_features, self.clip.logit_scale,
-                                                         group, True, self.clip.arena)
+            if keys is not None:
+                loss, t, i, lpt, lpi = T.KeyedContrastiveFn.apply(text_features, image_features, self.clip.logit_scale,
+                                                                  keys, group, True, self.clip.arena)
+            else:
+                loss, t, i, lpt, lpi = T.ContrastiveFn.apply(text_features, image_features, self.clip.logit_scale,
+                                                             group, True, self.clip.arena)
             world = CM.world_rank(group)[0]
             return {"loss": loss, "text_features": t, "image_features": i, "logits_per_text": lpt,
                     "logits_per_image": lpt.t() if world == 1 and lpt is not None else lpi}

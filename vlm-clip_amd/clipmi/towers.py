@@ -17,6 +17,7 @@ Reference mapping:
                     peclip.TextualAdapter (adapter/peclip.py:13-18) with ln=False
   PoolProjFn     <- [:, 0, :] + text_projection / visual_projection (model_m.py:102-103, 122-123)
   ContrastiveFn  <- model_m.py:146-171 (+ the SURVEY §8e data-parallel all-gather form)
+  KeyedContrastiveFn  the same with the positives of a row given by a key per pair (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -175,6 +176,14 @@ _lib.declare("clipmi_contrastive_ce_fwd_chunk", [c_vp, c_vp, c_vp, c_int, c_int,
 _lib.declare("clipmi_contrastive_ce_finish", [c_vp, c_vp, c_vp, c_int, c_vp, c_vp])
 _lib.declare("clipmi_contrastive_ce_bwd_chunk", [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
                                                  c_float, c_vp, c_vp, c_int])
+_lib.declare("clipmi_contrastive_keyed_fwd", [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_contrastive_keyed_bwd", [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float,
+                                              c_vp, c_vp])
+_lib.declare("clipmi_contrastive_keyed_fwd_chunk", [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp])
+_lib.declare("clipmi_contrastive_keyed_finish", [c_vp, c_vp, c_int, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_contrastive_keyed_bwd_chunk", [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                                                    c_int, c_int, c_float, c_vp, c_vp, c_int])
+_lib.declare("clipmi_row_hash64", [c_vp, c_vp, c_int, c_int, c_vp])
 _lib.declare("clipmi_cast_f32_bf16", [c_vp, c_vp, c_vp, c_i64])
 _lib.declare("clipmi_grad_norm_ws", [], c_i64)
 _lib.declare("clipmi_grad_norm", [c_vp, c_vp, c_i64, c_float, c_vp, c_vp, c_i64])
@@ -854,6 +863,14 @@ def _gather(x, group, world):
     return torch.cat(parts)
 
 
+def _gather_keys(keys, group, world):
+    """All-gather the int64 pair keys in rank order.  A Communicator's all-gather carries fp32 / bf16 only, so the
+    keys travel as their bit pattern viewed as fp32 [B, 2] (a copy, no arithmetic); torch groups gather int64."""
+    if CM.is_lib(group) and (world > 1 or force_collectives()):
+        return group.all_gather(keys.contiguous().view(torch.float32).view(-1, 2)).view(torch.int64).view(-1)
+    return _gather(keys, group, world)
+
+
 def _reduce_scatter(x, group, world):
     """Sum over the group, keep this rank's row block (RCCL reduce_scatter_tensor; gloo:
     all_reduce + slice, which gloo supports for device tensors)."""
@@ -886,12 +903,21 @@ def contrastive_chunk(world=2):
     return max(1, int(env or "8192"))
 
 
-def _ce_streamed_fwd(s, x_local, y_all, ls, lab0, C, lse, ce):
-    """Row-wise CE of logits = exp(ls) * x_local y_all^T over column chunks of width C."""
+def _ce_streamed_fwd(s, x_local, y_all, ls, lab0, C, lse, ce, keys=None, winv=None):
+    """Row-wise CE of logits = exp(ls) * x_local y_all^T over column chunks of width C.  keys (int64 [Bg]): the
+    multi-positive form, which also writes winv."""
     B, E = x_local.shape
     Bg = y_all.shape[0]
     dev = x_local.device
     sbuf = torch.empty(B * min(C, Bg), dtype=torch.float32, device=dev)
+    if keys is not None:
+        run = torch.empty(B, 4, dtype=torch.float32, device=dev)
+        for c0 in range(0, Bg, C):
+            cw = min(C, Bg - c0)
+            _gemm_f32(B, cw, E, x_local, E, True, y_all[c0:], E, True, sbuf, cw)
+            call("clipmi_contrastive_keyed_fwd_chunk", s, P_(sbuf), P_(ls), P_(keys), B, cw, c0, Bg, lab0, P_(run))
+        call("clipmi_contrastive_keyed_finish", s, P_(run), B, P_(lse), P_(ce), P_(winv))
+        return
     run = torch.empty(B, 2, dtype=torch.float32, device=dev)
     lab = torch.empty(B, dtype=torch.float32, device=dev)
     for c0 in range(0, Bg, C):
@@ -901,10 +927,10 @@ def _ce_streamed_fwd(s, x_local, y_all, ls, lab0, C, lse, ce):
     call("clipmi_contrastive_ce_finish", s, P_(run), P_(lab), B, P_(lse), P_(ce))
 
 
-def _ce_streamed_bwd(s, x_local, y_all, ls, gl, lse, lab0, norm, C, dls, dy_all, dx_local):
+def _ce_streamed_bwd(s, x_local, y_all, ls, gl, lse, lab0, norm, C, dls, dy_all, dx_local, keys=None, winv=None):
     """Gradients of the streamed CE: dy_all[j] = sum_i dS[i, j] x_local[i] (column direction,
     every chunk writes its own rows) and dx_local = sum_j dS[:, j] y_all[j] (row direction,
-    accumulated over the chunks), recomputing each chunk's cosines."""
+    accumulated over the chunks), recomputing each chunk's cosines.  keys, winv: the multi-positive form."""
     B, E = x_local.shape
     Bg = y_all.shape[0]
     dev = x_local.device
@@ -913,8 +939,12 @@ def _ce_streamed_bwd(s, x_local, y_all, ls, gl, lse, lab0, norm, C, dls, dy_all,
     for n, c0 in enumerate(range(0, Bg, C)):
         cw = min(C, Bg - c0)
         _gemm_f32(B, cw, E, x_local, E, True, y_all[c0:], E, True, sbuf, cw)
-        call("clipmi_contrastive_ce_bwd_chunk", s, P_(sbuf), P_(lse), P_(ls), P_(gl), B, cw, c0, Bg, lab0, norm,
-             P_(dbuf), P_(dls), 1 if n else 0)
+        if keys is not None:
+            call("clipmi_contrastive_keyed_bwd_chunk", s, P_(sbuf), P_(lse), P_(winv), P_(ls), P_(gl), P_(keys), B, cw,
+                 c0, Bg, lab0, norm, P_(dbuf), P_(dls), 1 if n else 0)
+        else:
+            call("clipmi_contrastive_ce_bwd_chunk", s, P_(sbuf), P_(lse), P_(ls), P_(gl), B, cw, c0, Bg, lab0, norm,
+                 P_(dbuf), P_(dls), 1 if n else 0)
         _gemm_f32(cw, E, B, dbuf, cw, False, x_local, E, False, dy_all[c0:], E)
         _gemm_f32(B, E, cw, dbuf, cw, True, y_all[c0:], E, False, dx_local, E, flags=_lib.EPI_BETA if n else 0)
 
@@ -929,7 +959,14 @@ class ContrastiveFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tf, imf, logit_scale, group, global_loss, arena):
+        return ContrastiveFn.run(ctx, tf, imf, logit_scale, group, global_loss, arena, None)
+
+    @staticmethod
+    def run(ctx, tf, imf, logit_scale, group, global_loss, arena, keys):
+        """keys: None, or this rank's int64 [B] pair keys on the device (KeyedContrastiveFn): the multi-positive
+        kernels (csrc/contrastive_keys.hip) take the place of the diagonal ones, everything around them is shared."""
         world, rank = CM.world_rank(group)
+        ctx.nin = 6 if keys is None else 7
         B, E = tf.shape
         dev = tf.device
         s = K.stream()
@@ -945,17 +982,27 @@ class ContrastiveFn(torch.autograd.Function):
         C = contrastive_chunk(world)
         ls = logit_scale.detach().reshape(1)
         lab0 = rank * B
+        kg = winv = None
+        keyed = ()
+        if keys is not None:
+            kg = _gather_keys(keys, group, world)  # rank order, as the features
+            winv = torch.empty(2, B, dtype=torch.float32, device=dev)  # 1 / |P_i| per row and direction
+            keyed = (kg, winv)
         if Bg > C:
             lse = torch.empty(2, B, dtype=torch.float32, device=dev)
             ce = torch.empty(2, B, dtype=torch.float32, device=dev)
-            _ce_streamed_fwd(s, th, ig, ls, lab0, C, lse[0], ce[0])
-            _ce_streamed_fwd(s, ih, tg, ls, lab0, C, lse[1], ce[1])
+            if keys is not None:
+                _ce_streamed_fwd(s, th, ig, ls, lab0, C, lse[0], ce[0], kg, winv[0])
+                _ce_streamed_fwd(s, ih, tg, ls, lab0, C, lse[1], ce[1], kg, winv[1])
+            else:
+                _ce_streamed_fwd(s, th, ig, ls, lab0, C, lse[0], ce[0])
+                _ce_streamed_fwd(s, ih, tg, ls, lab0, C, lse[1], ce[1])
             loss = torch.empty((), dtype=torch.float32, device=dev)
             call("clipmi_sum2", s, P_(ce[0]), P_(ce[1]), B, 1.0 / (2 * Bg), P_(loss), 0)
             loss_out = loss
             if world > 1 and global_loss:
                 loss_out = CM.all_reduce_(loss.clone(), group)
-            ctx.save_for_backward(th, ih, tn, inn, tg, ig, lse, ls)
+            ctx.save_for_backward(th, ih, tn, inn, tg, ig, lse, ls, *keyed)
             ctx.group, ctx.world, ctx.B, ctx.Bg, ctx.lab0, ctx.chunk = group, world, B, Bg, lab0, C
             ctx.ls_param, ctx.arena = logit_scale, arena
             return loss_out, th, ih, None, None
@@ -966,8 +1013,13 @@ class ContrastiveFn(torch.autograd.Function):
         _gemm_f32(B, Bg, E, ih, E, True, tg, E, True, li, Bg)   # cos(i_local, t_all)
         lse = torch.empty(2, B, dtype=torch.float32, device=dev)
         ce = torch.empty(2, B, dtype=torch.float32, device=dev)
-        call("clipmi_contrastive_ce_fwd", s, P_(lt), P_(lt), P_(ls), B, Bg, lab0, P_(lse[0]), P_(ce[0]))
-        call("clipmi_contrastive_ce_fwd", s, P_(li), P_(li), P_(ls), B, Bg, lab0, P_(lse[1]), P_(ce[1]))
+        if keys is not None:
+            for blk, n in ((lt, 0), (li, 1)):
+                call("clipmi_contrastive_keyed_fwd", s, P_(blk), P_(blk), P_(ls), P_(kg), B, Bg, lab0, P_(lse[n]),
+                     P_(ce[n]), P_(winv[n]))
+        else:
+            call("clipmi_contrastive_ce_fwd", s, P_(lt), P_(lt), P_(ls), B, Bg, lab0, P_(lse[0]), P_(ce[0]))
+            call("clipmi_contrastive_ce_fwd", s, P_(li), P_(li), P_(ls), B, Bg, lab0, P_(lse[1]), P_(ce[1]))
         loss = torch.empty((), dtype=torch.float32, device=dev)
         call("clipmi_sum2", s, P_(ce[0]), P_(ce[1]), B, 1.0 / (2 * Bg), P_(loss), 0)
         if world > 1 and global_loss:
@@ -976,7 +1028,7 @@ class ContrastiveFn(torch.autograd.Function):
             loss_out = loss
         # outputs (th, ih, lt, li) must go through save_for_backward: keeping them as plain ctx
         # attributes forms node -> ctx -> output -> grad_fn -> node, a cycle that leaks the graph
-        ctx.save_for_backward(th, ih, tn, inn, tg, ig, lt, li, lse, ls)
+        ctx.save_for_backward(th, ih, tn, inn, tg, ig, lt, li, lse, ls, *keyed)
         ctx.group, ctx.world, ctx.B, ctx.Bg, ctx.lab0 = group, world, B, Bg, lab0
         ctx.ls_param, ctx.arena = logit_scale, arena
         ctx.mark_non_differentiable(lt, li)
@@ -986,7 +1038,8 @@ class ContrastiveFn(torch.autograd.Function):
     def backward(ctx, gloss, gth, gih, glt, gli):
         if ctx.chunk is not None:
             return ContrastiveFn._backward_streamed(ctx, gloss, gth, gih)
-        th, ih, tn, inn, tg, ig, lt, li, lse, ls = ctx.saved_tensors
+        th, ih, tn, inn, tg, ig, lt, li, lse, ls = ctx.saved_tensors[:10]
+        keyed = ctx.saved_tensors[10:]  # (gathered keys, winv) of the multi-positive form
         B, Bg, E, world = ctx.B, ctx.Bg, th.shape[1], ctx.world
         dev = th.device
         s = K.stream()
@@ -995,8 +1048,14 @@ class ContrastiveFn(torch.autograd.Function):
         dSi = torch.empty(B, Bg, dtype=torch.float32, device=dev)
         dls = torch.empty(2, B, dtype=torch.float32, device=dev)
         norm = 1.0 / (2 * Bg)
-        call("clipmi_contrastive_ce_bwd", s, P_(lt), P_(lse[0]), P_(ls), P_(gl), B, Bg, ctx.lab0, norm, P_(dSt), P_(dls[0]))
-        call("clipmi_contrastive_ce_bwd", s, P_(li), P_(lse[1]), P_(ls), P_(gl), B, Bg, ctx.lab0, norm, P_(dSi), P_(dls[1]))
+        if keyed:
+            kg, winv = keyed
+            for blk, dS, n in ((lt, dSt, 0), (li, dSi, 1)):
+                call("clipmi_contrastive_keyed_bwd", s, P_(blk), P_(lse[n]), P_(winv[n]), P_(ls), P_(gl), P_(kg), B, Bg,
+                     ctx.lab0, norm, P_(dS), P_(dls[n]))
+        else:
+            call("clipmi_contrastive_ce_bwd", s, P_(lt), P_(lse[0]), P_(ls), P_(gl), B, Bg, ctx.lab0, norm, P_(dSt), P_(dls[0]))
+            call("clipmi_contrastive_ce_bwd", s, P_(li), P_(lse[1]), P_(ls), P_(gl), B, Bg, ctx.lab0, norm, P_(dSi), P_(dls[1]))
         # dt^ = dSt i_all + (dSi^T i_local)[rank rows] ; di^ = dSi t_all + (dSt^T t_local)[rank rows]
         # column-direction terms first (reduce-scattered to their owners), then the row terms
         # accumulate on top through the GEMM's beta epilogue
@@ -1012,7 +1071,8 @@ class ContrastiveFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_streamed(ctx, gloss, gth, gih):
-        th, ih, tn, inn, tg, ig, lse, ls = ctx.saved_tensors
+        th, ih, tn, inn, tg, ig, lse, ls = ctx.saved_tensors[:8]
+        kg, winv = ctx.saved_tensors[8:] or (None, (None, None))
         B, Bg, E, world, C = ctx.B, ctx.Bg, th.shape[1], ctx.world, ctx.chunk
         dev = th.device
         s = K.stream()
@@ -1024,8 +1084,8 @@ class ContrastiveFn(torch.autograd.Function):
         dIg = torch.empty(Bg, E, dtype=torch.float32, device=dev)
         dth_row = torch.empty(B, E, dtype=torch.float32, device=dev)
         dih_row = torch.empty(B, E, dtype=torch.float32, device=dev)
-        _ce_streamed_bwd(s, th, ig, ls, gl, lse[0], ctx.lab0, norm, C, dls[0], dIg, dth_row)
-        _ce_streamed_bwd(s, ih, tg, ls, gl, lse[1], ctx.lab0, norm, C, dls[1], dTg, dih_row)
+        _ce_streamed_bwd(s, th, ig, ls, gl, lse[0], ctx.lab0, norm, C, dls[0], dIg, dth_row, kg, winv[0])
+        _ce_streamed_bwd(s, ih, tg, ls, gl, lse[1], ctx.lab0, norm, C, dls[1], dTg, dih_row, kg, winv[1])
         dth = _reduce_scatter(dTg, ctx.group, world)
         dih = _reduce_scatter(dIg, ctx.group, world)
         dth += dth_row
@@ -1050,4 +1110,18 @@ class ContrastiveFn(torch.autograd.Function):
         di = torch.empty(B, E, dtype=torch.float32, device=dev)
         call("clipmi_l2norm_bwd", s, P_(dth), P_(th), P_(tn), P_(dt), B, E)
         call("clipmi_l2norm_bwd", s, P_(dih), P_(ih), P_(inn), P_(di), B, E)
-        return dt, di, None, None, None, None
+        return (dt, di) + (None,) * (ctx.nin - 2)
+
+
+class KeyedContrastiveFn(ContrastiveFn):
+    """ContrastiveFn with the positives of a row given by a key per pair (multi-positive InfoNCE, SupCon's L_out in both
+    directions; csrc/contrastive_keys.hip): pairs of the global batch with equal keys are each other's positives,
+    ce_i = lse_i - mean of the positive logits.  keys: this rank's int64 [B] on the device; in a data-parallel
+    group they are all-gathered in rank order alongside the features.  With all keys distinct the loss and every
+    gradient are bit for bit ContrastiveFn's, in the materialised, the streamed and the data-parallel form."""
+
+    @staticmethod
+    def forward(ctx, tf, imf, logit_scale, keys, group, global_loss, arena):
+        if keys.dtype != torch.int64 or keys.dim() != 1 or keys.shape[0] != tf.shape[0] or keys.device != tf.device:
+            raise ValueError(f"pair keys must be an int64 tensor of length {tf.shape[0]} on the features' device")
+        return ContrastiveFn.run(ctx, tf, imf, logit_scale, group, global_loss, arena, keys.contiguous())

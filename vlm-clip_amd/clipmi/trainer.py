@@ -19,6 +19,7 @@ from . import comm as CM
 from . import kernels as K
 from . import towers as T
 from .images import ImageBatch
+from .losses import batch_keys
 
 
 def linear_schedule_with_warmup(step, warmup, total):
@@ -243,12 +244,21 @@ def _to_device(batch, device, non_blocking):
 class CLIPAdapterTrainer:
     """trainer.py:11-167.  ``trainable="adapter"`` selects parameters whose name contains
     "adapter" exactly like trainer.py:40-43; ``trainable="requires_grad"`` takes every
-    parameter with requires_grad (full fine-tune)."""
+    parameter with requires_grad (full fine-tune).
+
+    ``positives`` (no reference counterpart) chooses the positives of the contrastive loss in train_step and
+    evaluate(): None, the reference's diagonal loss; "caption", pairs whose token rows are equal (hashed on the
+    device); any other string, a batch field holding an int tensor or a list of strings, e.g. "emotion" as the
+    default collate delivers RAFDBDataset's; or a callable batch -> keys (clipmi.losses.batch_keys).  Pairs of the
+    global batch with equal keys are each other's positives (towers.KeyedContrastiveFn)."""
 
     def __init__(self, model, train_dataloader, val_dataloader=None, learning_rate=5e-5, weight_decay=0.01,
                  warmup_steps=0, max_grad_norm=1.0, output_dir="./clip_adapter_checkpoints", *,
-                 trainable="adapter", process_group=None, augment=None):
+                 trainable="adapter", process_group=None, augment=None, positives=None):
         self.model = model
+        if positives is not None and not (isinstance(positives, str) or callable(positives)):
+            raise ValueError("positives: None, 'caption', a batch field name or a callable batch -> keys")
+        self.positives = positives
         # ImageBatch -> ImageBatch (clipmi.images.TrainAugment), applied by train_step only; no reference counterpart
         self.augment = augment
         self.train_dataloader = train_dataloader
@@ -282,6 +292,11 @@ class CLIPAdapterTrainer:
             return dist.get_world_size()
         return CM.world_rank(self.process_group)[0]
 
+    def _loss_kwargs(self, batch, device):
+        """pair_keys of the batch under the positives switch; nothing at all for the diagonal loss."""
+        keys = batch_keys(batch, self.positives, device)
+        return {} if keys is None else {"pair_keys": keys}
+
     def train_step(self, batch, step, total_steps):
         """One reference step (trainer.py:81-99); returns the loss tensor (no host sync)."""
         device = self.model.clip.arena.device
@@ -289,7 +304,8 @@ class CLIPAdapterTrainer:
         if self.augment is not None and isinstance(batch.get("pixel_values"), ImageBatch):
             batch["pixel_values"] = self.augment(batch["pixel_values"])
         outputs = self.model(input_ids=batch.get("input_ids"), attention_mask=batch.get("attention_mask"),
-                             pixel_values=batch.get("pixel_values"), return_loss=True)
+                             pixel_values=batch.get("pixel_values"), return_loss=True,
+                             **self._loss_kwargs(batch, device))
         loss = outputs["loss"]
         self.optimizer.zero_grad()
         self.optimizer.armed_backward(loss)
@@ -333,7 +349,8 @@ class CLIPAdapterTrainer:
             for batch in self.val_dataloader:
                 batch = _to_device(batch, device, False)
                 outputs = self.model(input_ids=batch.get("input_ids"), attention_mask=batch.get("attention_mask"),
-                                     pixel_values=batch.get("pixel_values"), return_loss=True)
+                                     pixel_values=batch.get("pixel_values"), return_loss=True,
+                                     **self._loss_kwargs(batch, device))
                 val_loss += outputs["loss"].item()
         return val_loss / len(self.val_dataloader)
 
