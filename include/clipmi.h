@@ -36,7 +36,8 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
  * 4: clipmi_topk_merge
  * 5: clipmi_encoder_desc gained cls_last (appended); clipmi_attention_cls_fwd / _bwd, clipmi_layernorm_bwd4
  * 6: clipmi_resize_crop_u8 (ragged image batches)
- * 7: clipmi_contrastive_keyed_* (multi-positive contrastive head), clipmi_row_hash64 */
+ * 7: clipmi_contrastive_keyed_* (multi-positive contrastive head), clipmi_row_hash64
+ * 8: clipmi_group_pick, clipmi_group_count, clipmi_topk_hits (group-aware retrieval evaluation) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -592,6 +593,35 @@ int clipmi_rank_count(void* stream, const float* S, int64_t lds, int N, int M, i
 #define CLIPMI_TOPK_MAX 256
 int clipmi_topk_merge(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols,
                       int k, int first, const int64_t* exclude, float* top_score, int* top_idx);
+/* Group-aware ranks over the same streamed blocks (csrc/eval_keys.hip; clipmi_version() >= 8): the positives of
+ * query i are all candidates j with ckeys[j] == qkeys[i] (int64 [M] / [N], both non-null, compared as full 64-bit
+ * values), the keys of the multi-positive contrastive head.  exclude (int64 [N] or NULL): candidate exclude[i] is
+ * neither a positive nor a negative nor a top1 of query i (the query itself when both sides are one set); a
+ * value outside [0, M) excludes nothing, as in clipmi_topk_merge.  S, lds, N, M, the block ranges, `first`, the
+ * output indexing, the stream rule and the load paths are those of clipmi_rank_count.
+ *   group_pick   over the block's positives, (pos_score[i], pos_idx[i]) = the best positive so far (highest score,
+ *                lowest candidate index on equal scores) and n_pos[i] = the number of positives so far; a row with
+ *                none yet holds pos_idx -1, pos_score -inf, n_pos 0.
+ *   group_count  after group_pick has seen every column block of the row range: greater[i] / equal[i] (+)=
+ *                #{ j in the block, not excluded, ckeys[j] != qkeys[i] : S[i, j] > / == pos_score[i] }, and
+ *                (top1[i], top1_score[i]) = the row maximum over the non-excluded candidates so far, lowest index
+ *                on ties (with exclude == NULL exactly clipmi_rank_count's).  A row with n_pos[i] == 0 gets
+ *                greater = equal = -1 on `first` and keeps them; its top1 is still maintained.
+ * Both passes need the SAME clipmi_gemm call per block, as rank_pick / rank_count: pos_score is a copy of an
+ * element of the block the counts compare against, so a negative that duplicates the best positive counts in
+ * `equal`, never in `greater`. */
+int clipmi_group_pick(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols,
+                      const int64_t* qkeys, const int64_t* ckeys, const int64_t* exclude, int first,
+                      float* pos_score, int* pos_idx, int* n_pos);
+int clipmi_group_count(void* stream, const float* S, int64_t lds, int N, int M, int row0, int rows, int col0, int cols,
+                       const int64_t* qkeys, const int64_t* ckeys, const int64_t* exclude, const float* pos_score,
+                       const int* n_pos, int first, int* greater, int* equal, int* top1, float* top1_score);
+/* Relevance of the lists clipmi_topk_merge wrote: hits[i][r] (int32 [N, k]) = #{ r' <= r : top_idx[i][r'] in
+ * [0, M) and ckeys[top_idx[i][r']] == qkeys[i] }, the inclusive prefix count behind precision@k and average
+ * precision.  An empty slot (-1) or an index >= M is no hit and is never used to read ckeys.
+ * 1 <= k <= CLIPMI_TOPK_MAX. */
+int clipmi_topk_hits(void* stream, const int* top_idx, int N, int k, int M, const int64_t* qkeys,
+                     const int64_t* ckeys, int* hits);
 /* One batch of the reference's classification loops (evaluation.py:43-54, utils.py:48-61): pred[b] = argmax_c
  * probs[b, c] (lowest index on ties), conf[b] its probability (torch.max(probs, 1)), and
  * confusion[labels[b] * C + pred[b]] += 1 (int64 [C, C], rows = true class as sklearn's confusion_matrix;

@@ -354,14 +354,16 @@ class CLIPAdapterTrainer:
                 val_loss += outputs["loss"].item()
         return val_loss / len(self.val_dataloader)
 
-    def evaluate_retrieval(self, ks=(1, 5, 10), topk=0):
+    def evaluate_retrieval(self, ks=(1, 5, 10), topk=0, keys=None):
         """Recall@K and median / mean rank (image->text and text->image) over the whole validation set, on the
         device (clipmi.evaluation.evaluate_retrieval); unlike evaluate()'s mean batch loss it does not depend
-        on the batch size.  topk > 0 adds the top-k retrieved lists (``i2t_topk`` / ``t2i_topk``).  No reference
-        counterpart."""
+        on the batch size.  topk > 0 adds the top-k retrieved lists (``i2t_topk`` / ``t2i_topk``).  keys adds
+        the group-aware metrics (``_gR@k``, ``_g_median_rank``, ``_P@k``, ``_mAP@k``), in which every pair that
+        shares a pair's key is a correct retrieval: a model trained with ``positives=...`` is usually scored with
+        ``keys=trainer.positives``.  The default scores the diagonal alone.  No reference counterpart."""
         assert self.val_dataloader is not None, "val_dataloader must not be None to run eval"
         from .evaluation import evaluate_retrieval
-        return evaluate_retrieval(self.model, self.val_dataloader, ks=ks, topk=topk)
+        return evaluate_retrieval(self.model, self.val_dataloader, ks=ks, topk=topk, keys=keys)
 
     def save_model(self, path):
         self.model.save_adapter_weights(f"{path}.pt")
