@@ -37,7 +37,8 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
  * 5: clipmi_encoder_desc gained cls_last (appended); clipmi_attention_cls_fwd / _bwd, clipmi_layernorm_bwd4
  * 6: clipmi_resize_crop_u8 (ragged image batches)
  * 7: clipmi_contrastive_keyed_* (multi-positive contrastive head), clipmi_row_hash64
- * 8: clipmi_group_pick, clipmi_group_count, clipmi_topk_hits (group-aware retrieval evaluation) */
+ * 8: clipmi_group_pick, clipmi_group_count, clipmi_topk_hits (group-aware retrieval evaluation)
+ * 9: clipmi_color_u8 (colour augmentation of the input step) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -263,6 +264,47 @@ typedef struct clipmi_image_item {
 int64_t clipmi_resize_crop_u8_ws(const clipmi_image_item* items, int B, int S, int mode);
 int clipmi_resize_crop_u8(void* stream, const uint8_t* packed, int64_t packed_bytes, const clipmi_image_item* items,
                           int B, uint8_t* out, int S, int mode, void* ws, int64_t ws_bytes);
+/* Colour augmentation (csrc/color.hip; clipmi_version() >= 9): torchvision's ColorJitter and RandomGrayscale on PIL
+ * images, bit for bit, on channels-last RGB uint8 [B, H, W, 3] in place; each image has its own factors and its own
+ * order of the ops.  It runs on clipmi_resize_crop_u8's output: after the resize, the window and the flip.
+ *   L(R, G, B)     = (19595 R + 38470 G + 7471 B + 32768) >> 16                             (PIL convert("L"))
+ *   blend(d, x, a) = t = fl32(fl32(d) + fl32(a * fl32(x - d))): x - d an integer, the product and the sum two
+ *                    separately rounded float32 operations (no fma); trunc(t) when 0 <= a <= 1, else 0 where t <= 0,
+ *                    255 where t >= 255, trunc(t) between                                   (PIL Image.blend)
+ *   brightness f:  blend(0, x, f) per channel                                               (ImageEnhance.Brightness)
+ *   contrast f:    blend(m, x, f), m = floor((2 sum L + n) / (2n)) = int(mean L + 0.5) over the image's n pixels in
+ *                  their state after the ops in front of it; an integer sum                 (ImageEnhance.Contrast)
+ *   saturation f:  blend(L(pixel), x, f)                                                    (ImageEnhance.Color)
+ *   hue shift k:   PIL RGB -> HSV, H = (H + k) mod 256, PIL HSV -> RGB; a listed hue op does the round trip at k = 0
+ *                  too (it is not the identity).  float32 unless marked:
+ *                  RGB -> HSV: V = mx; mx == mn: H = S = 0; else cr = fl32(mx - mn), s = cr / fl32(mx),
+ *                    rc, gc, bc = fl32(mx - c) / cr; h = bc - gc if R == mx, else 2.0 + rc - bc (double) if G == mx,
+ *                    else 4.0 + gc - rc (double), rounded to float32; h = fl32(fmod(double(h) / 6.0 + 1.0, 1.0));
+ *                    H = clip(int(double(h) * 255.0)), S = clip(int(double(s) * 255.0))
+ *                  HSV -> RGB: S == 0: R = G = B = V; else x = double(fl32(H)) * 6.0 / 255.0, i = floor(x),
+ *                    f = fl32(x - i), fs = fl32(double(S) / 255.0); in double, rounded half away from zero and
+ *                    clipped: p = V (1 - fs), q = V (1 - fs f), t = V (1 - fs (1 - f)); (R, G, B) by i mod 6:
+ *                    (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q)
+ *   gray:          after the list, R = G = B = L(pixel)                                     (convert("L") x 3)
+ * `order` lists up to four op codes, 4 bits each, the first op in the low nibble, 0 ends the list; a code appears at
+ * most once (so an image has at most one contrast mean).  An item with an empty list and gray = 0 leaves its image's
+ * bytes untouched.  `items` is host memory: every item is validated before any launch (NaN, an infinity or a negative
+ * factor, hue_shift outside 0..255, an unknown or repeated code, a code after the terminator, gray outside {0, 1}
+ * return CLIPMI_ERR_INVALID naming the item; H * W > 2^24, the range of the 32-bit luma sum, is rejected too) and the
+ * per-image records are uploaded into the workspace on the stream; the kernels read that copy only.  Two launches
+ * whatever B is: the luma sums of the images with a contrast (integer atomics: bitwise reproducible), then every
+ * pixel through its image's list.  B == 0 returns.  clipmi_color_u8_ws returns the workspace bytes (a negative status
+ * on invalid items); the workspace must be 16-byte aligned. */
+typedef struct clipmi_color_item {
+  float   brightness, contrast, saturation; /* blend factors: finite, >= 0 */
+  int32_t hue_shift;                        /* 0..255 */
+  int32_t order;   /* up to four op codes, 4 bits each, first op in the low nibble, 0 ends the list;
+                      1 brightness, 2 contrast, 3 saturation, 4 hue; a code at most once */
+  int32_t gray;    /* 0 | 1 */
+} clipmi_color_item;
+int64_t clipmi_color_u8_ws(const clipmi_color_item* items, int B, int H, int W);
+int clipmi_color_u8(void* stream, uint8_t* images /* [B,H,W,3], in place */, const clipmi_color_item* items,
+                    int B, int H, int W, void* ws, int64_t ws_bytes);
 /* pooled token per row: mode 0 first token (model_m.py:102), 1 first EOS (0 when the row has none), 2 argmax id,
  * the first of tied maxima ([HF] :561-581).  gather: out[b] = src[b*S + idx[b]]; scatter: dst[b*S + idx[b]] (+)=
  * src[b], the other rows of dst untouched; idx NULL: token 0.  B = 0 is a no-op. */

@@ -14,7 +14,14 @@ then the flip, applied to the output's columns.  Downscales above 32x per axis a
 
 Augmentation (no reference counterpart: the reference trains without any): ``random_resized_crop_boxes``
 is the published RandomResizedCrop.get_params algorithm, ``TrainAugment`` draws boxes and flips from
-its own seeded generator, ``CLIPAdapterTrainer(augment=...)`` applies it in ``train_step`` only."""
+its own seeded generator, ``CLIPAdapterTrainer(augment=...)`` applies it in ``train_step`` only.
+
+Colour: ``color_jitter_u8`` runs torchvision's ColorJitter / RandomGrayscale as they act on PIL images
+(ImageEnhance.Brightness / Contrast / Color, the 8-bit HSV hue shift, convert("L")) bit for bit on uint8
+[B, H, W, 3] in place, each image with its own factors and op order (include/clipmi.h clipmi_color_u8: two
+launches whatever B is).  ``ColorJitter`` samples the per-image records as ColorJitter.get_params does;
+an ``ImageBatch`` that carries records (``with_color``) gets them applied by ``preprocess`` after the
+resize, the window and the flip."""
 from __future__ import annotations
 
 import ctypes
@@ -35,11 +42,47 @@ class ImageItem(ctypes.Structure):
                 ("y0", ctypes.c_int32), ("cw", ctypes.c_int32), ("ch", ctypes.c_int32), ("flip", ctypes.c_int32)]
 
 
+class ColorItem(ctypes.Structure):
+    """include/clipmi.h clipmi_color_item.  ``ColorItem.of`` builds one from an op list."""
+    _fields_ = [("brightness", ctypes.c_float), ("contrast", ctypes.c_float), ("saturation", ctypes.c_float),
+                ("hue_shift", ctypes.c_int32), ("order", ctypes.c_int32), ("gray", ctypes.c_int32)]
+
+    @classmethod
+    def of(cls, ops=(), gray=0):
+        """ops: [(name, value)] in the order they run, name in COLOR_OPS, each at most once; value a blend factor
+        (brightness, contrast, saturation: 1 leaves the image as it is) or the hue shift 0..255 added to PIL's H."""
+        it = cls(1.0, 1.0, 1.0, 0, 0, int(gray))
+        if len(ops) > 4:
+            raise ValueError("ColorItem.of: at most four ops")
+        for k, (name, value) in enumerate(ops):
+            if name not in COLOR_OPS:
+                raise ValueError(f"ColorItem.of: op must be one of {sorted(COLOR_OPS)}, got {name!r}")
+            setattr(it, "hue_shift" if name == "hue" else name, int(value) if name == "hue" else float(value))
+            it.order |= COLOR_OPS[name] << (4 * k)
+        return it
+
+    def ops(self):
+        """[(name, value)] in the order they run."""
+        names = {v: k for k, v in COLOR_OPS.items()}
+        out, order = [], self.order
+        while order & 15:
+            name = names[order & 15]
+            out.append((name, self.hue_shift if name == "hue" else getattr(self, name)))
+            order >>= 4
+        return out
+
+
+COLOR_OPS = {"brightness": 1, "contrast": 2, "saturation": 3, "hue": 4}
+
 _lib.declare("clipmi_resize_crop_u8_ws", [ctypes.POINTER(ImageItem), ctypes.c_int, ctypes.c_int, ctypes.c_int],
              ctypes.c_int64)
 _lib.declare("clipmi_resize_crop_u8", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ImageItem),
                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_int64])
+_lib.declare("clipmi_color_u8_ws", [ctypes.POINTER(ColorItem), ctypes.c_int, ctypes.c_int, ctypes.c_int],
+             ctypes.c_int64)
+_lib.declare("clipmi_color_u8", [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ColorItem), ctypes.c_int,
+                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64])
 
 
 class ImageBatch:
@@ -47,9 +90,10 @@ class ImageBatch:
 
     ``data``: uint8 [sum h*w*3] (host, pinned when CUDA is available, or device after ``.to``);
     ``sizes``: [(h, w)]; ``offsets``: byte offset of each image; ``boxes``: [(x0, y0, cw, ch)] (default:
-    the whole image); ``flips``: [0 | 1] (default 0); ``mode``: "processor" | "square"."""
+    the whole image); ``flips``: [0 | 1] (default 0); ``mode``: "processor" | "square"; ``color``: one ColorItem
+    per image, applied to ``preprocess``'s output (default None: no colour pass)."""
 
-    def __init__(self, data, sizes, offsets, boxes=None, flips=None, mode="processor"):
+    def __init__(self, data, sizes, offsets, boxes=None, flips=None, mode="processor", color=None):
         if mode not in MODES:
             raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
         self.data = data
@@ -59,6 +103,9 @@ class ImageBatch:
         self.boxes = [(0, 0, w, h) for h, w in self.sizes] if boxes is None else [tuple(int(v) for v in b) for b in boxes]
         self.flips = [0] * n if flips is None else [int(f) for f in flips]
         self.mode = mode
+        self.color = None if color is None else list(color)
+        if self.color is not None and len(self.color) != n:
+            raise ValueError("ImageBatch: color must have one ColorItem per image")
         if not (len(self.offsets) == len(self.boxes) == len(self.flips) == n):
             raise ValueError("ImageBatch: sizes, offsets, boxes and flips must have one entry per image")
         if any(len(b) != 4 for b in self.boxes):
@@ -87,7 +134,7 @@ class ImageBatch:
 
     def _like(self, **kw):
         a = dict(data=self.data, sizes=self.sizes, offsets=self.offsets, boxes=self.boxes, flips=self.flips,
-                 mode=self.mode)
+                 mode=self.mode, color=self.color)
         a.update(kw)
         return ImageBatch(**a)
 
@@ -110,6 +157,9 @@ class ImageBatch:
     def with_mode(self, mode):
         return self._like(mode=mode)
 
+    def with_color(self, items):
+        return self._like(color=items)
+
     def items(self):
         """The clipmi_image_item table (host)."""
         arr = (ImageItem * max(len(self), 1))()
@@ -120,7 +170,8 @@ class ImageBatch:
 
 def preprocess(batch, image_size, mode=None, out=None):
     """ImageBatch (on the GPU) -> uint8 [B, S, S, 3] on its device, through clipmi_resize_crop_u8.  mode: the
-    batch's own when None.  out: a contiguous uint8 view of B*S*S*3 elements to write into."""
+    batch's own when None.  out: a contiguous uint8 view of B*S*S*3 elements to write into.  A batch with colour
+    records (``with_color``) gets them applied to the output in place (clipmi_color_u8, two more launches)."""
     mode = batch.mode if mode is None else mode
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
@@ -140,7 +191,43 @@ def preprocess(batch, image_size, mode=None, out=None):
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=batch.data.device)
         _lib.check(L.clipmi_resize_crop_u8(K.stream(), K.ptr(batch.data), batch.data.numel(), items, B, K.ptr(out), S,
                                            MODES[mode], K.ptr(ws), nb), "clipmi_resize_crop_u8")
-    return out.view(B, S, S, 3)
+    out = out.view(B, S, S, 3)
+    if batch.color is not None:
+        color_jitter_u8(out, batch.color)
+    return out
+
+
+def _color_table(items):
+    """A ColorItem sequence as the ctypes array the library takes."""
+    n = len(items)
+    if not all(isinstance(it, ColorItem) for it in items):
+        raise ValueError("colour records must be ColorItem (ColorItem.of, ColorJitter.sample)")
+    return (ColorItem * max(n, 1))(*items), n
+
+
+def color_jitter_u8(images, items):
+    """uint8 [B, H, W, 3] on the GPU through clipmi_color_u8, in place: image b through items[b]'s ops in their
+    order, then its grayscale.  Returns ``images``."""
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("color_jitter_u8: images must be uint8 [B, H, W, 3]")
+    if not images.is_cuda:
+        raise ValueError("color_jitter_u8 needs the images on the GPU; there is no CPU fallback")
+    if not images.is_contiguous():
+        raise ValueError("color_jitter_u8 works in place: images must be contiguous")
+    B, H, W = (int(v) for v in images.shape[:3])
+    table, n = _color_table(items)
+    if n != B:
+        raise ValueError(f"color_jitter_u8: {n} records for {B} images")
+    L = _lib.lib()
+    nb = int(L.clipmi_color_u8_ws(table, B, max(H, 1) if B == 0 else H, max(W, 1) if B == 0 else W))
+    if nb < 0:
+        _lib.check(nb, "clipmi_color_u8_ws")
+    if B == 0:
+        return images
+    with torch.cuda.device(images.device):
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=images.device)
+        _lib.check(L.clipmi_color_u8(K.stream(), K.ptr(images), table, B, H, W, K.ptr(ws), nb), "clipmi_color_u8")
+    return images
 
 
 def _uniform(generator, lo, hi):
@@ -185,18 +272,87 @@ def random_flips(B, p=0.5, generator=None):
     return [int(v) for v in (torch.rand(B, generator=generator) < p)]
 
 
-class TrainAugment:
-    """ImageBatch -> ImageBatch with a random-resized-crop box and a flip bit per image, ``mode="square"``.
-    Its own generator (``seed``) makes a run reproducible."""
+def _jitter_range(name, value, center, bound=None):
+    """torchvision's ColorJitter._check_input: a number v is [max(0, center - v), center + v] (hue: [-v, v]), a pair
+    is (lo, hi); None when the op is disabled (None, 0, or a range that is the centre alone)."""
+    if value is None:
+        return None
+    if isinstance(value, (int, float)):
+        if not math.isfinite(value) or value < 0:
+            raise ValueError(f"ColorJitter: {name} must be a finite number >= 0, got {value}")
+        lo, hi = center - float(value), center + float(value)
+        if bound is None:
+            lo = max(lo, 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        lo, hi = float(value[0]), float(value[1])
+    else:
+        raise ValueError(f"ColorJitter: {name} must be a number or a (lo, hi) pair, got {value!r}")
+    lim = (0.0, math.inf) if bound is None else bound
+    if not (math.isfinite(lo) and math.isfinite(hi) and lim[0] <= lo <= hi <= lim[1]):
+        raise ValueError(f"ColorJitter: {name} range ({lo}, {hi}) must be ordered and inside "
+                         f"[{lim[0]}, {lim[1]}]")
+    return None if lo == hi == center else (lo, hi)
 
-    def __init__(self, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0):
+
+def hue_shift_of(factor):
+    """A hue factor in [-0.5, 0.5] as the byte torchvision's PIL path adds to H: int(f * 255), truncated toward
+    zero, wrapped to 0..255."""
+    return int(factor * 255) % 256
+
+
+class ColorJitter:
+    """torchvision's ColorJitter (+ RandomGrayscale with probability ``grayscale_p``) as a sampler of per-image
+    ColorItem records.  ``brightness`` / ``contrast`` / ``saturation``: v for factors in [max(0, 1 - v), 1 + v], or
+    (lo, hi) with 0 <= lo <= hi; ``hue``: h for [-h, h] with 0 <= h <= 0.5, or a pair inside [-0.5, 0.5]; 0 / None
+    disables an op.  ``sample(B, generator)`` follows ColorJitter.get_params per image: a random permutation of the
+    ops, then a uniform factor for each enabled one (disabled ones are left out of the list), then the grayscale
+    coin when ``grayscale_p`` > 0; all from the CPU generator given, so a seed fixes the records."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, grayscale_p=0):
+        self.ranges = {"brightness": _jitter_range("brightness", brightness, 1.0),
+                       "contrast": _jitter_range("contrast", contrast, 1.0),
+                       "saturation": _jitter_range("saturation", saturation, 1.0),
+                       "hue": _jitter_range("hue", hue, 0.0, (-0.5, 0.5))}
+        self.grayscale_p = float(grayscale_p)
+        if not 0.0 <= self.grayscale_p <= 1.0:
+            raise ValueError(f"ColorJitter: grayscale_p must be in [0, 1], got {grayscale_p}")
+
+    def sample(self, B, generator=None):
+        names = list(COLOR_OPS)  # get_params' fn_idx numbering: brightness, contrast, saturation, hue
+        items = []
+        for _ in range(int(B)):
+            perm = torch.randperm(4, generator=generator).tolist()
+            vals = {}
+            for name in names:
+                r = self.ranges[name]
+                if r is not None:
+                    f = _uniform(generator, r[0], r[1])
+                    vals[name] = hue_shift_of(f) if name == "hue" else f
+            gray = int(float(torch.rand((), generator=generator)) < self.grayscale_p) if self.grayscale_p > 0 else 0
+            items.append(ColorItem.of([(names[i], vals[names[i]]) for i in perm if names[i] in vals], gray))
+        return items
+
+
+class TrainAugment:
+    """ImageBatch -> ImageBatch with a random-resized-crop box and a flip bit per image, ``mode="square"``, and,
+    with ``color`` (a ColorJitter), a colour record per image.  Its own generator (``seed``) makes a run
+    reproducible; the colour records are drawn after the boxes and the flips, so a seed gives the same boxes and
+    flips with or without colour."""
+
+    def __init__(self, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0, color=None):
         self.scale, self.ratio, self.flip_p = tuple(scale), tuple(ratio), float(flip_p)
         self.generator = torch.Generator(device="cpu").manual_seed(int(seed))
+        if color is not None and not isinstance(color, ColorJitter):
+            raise ValueError("TrainAugment: color must be a ColorJitter or None")
+        self.color = color
 
     def __call__(self, batch):
         boxes = random_resized_crop_boxes(batch.sizes, self.scale, self.ratio, self.generator)
         flips = random_flips(len(batch), self.flip_p, self.generator)
-        return batch.with_boxes(boxes).with_flips(flips).with_mode("square")
+        out = batch.with_boxes(boxes).with_flips(flips).with_mode("square")
+        if self.color is not None:
+            out = out.with_color(self.color.sample(len(batch), self.generator))
+        return out
 
 
 def collate(samples):
