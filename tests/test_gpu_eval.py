@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 from clipmi import CLIPAdapterTrainer, CLIPWithAdapters, synth  # noqa: E402
 from clipmi import evaluation as EV  # noqa: E402
 from clipmi import heads as HD  # noqa: E402
+from clipmi import towers as T  # noqa: E402
 from heads_common import LN100, fixture, weights  # noqa: E402
 
 EMOS = ["angry", "disgust", "fear", "happy", "neutral", "sad", "surprise"]  # reference constants.EMOTIONS
@@ -87,6 +88,61 @@ def test_paired_integer_ranks_are_exact():
     assert_bitwise(got, host(EV.target_ranks(cuda(q), cuda(c), cuda(target), block=128)))  # explicit t_i = i
     with pytest.raises(ValueError):
         EV.target_ranks(cuda(q), cuda(c[:100]))  # paired needs N == M
+
+
+# the (rows, cols, E) of every GEMM call, in order, at N = 40 and E = 8: block 16 cuts 40 into 16 + 16 + 8 and 24
+# into 16 + 8, block 64 leaves one block
+GEMM_SCHEDULE = {
+    # paired, M = 40: per row range its diagonal block (pass 1), then the three column blocks (pass 2)
+    ("paired", 16): [(16, 16, 8), (16, 16, 8), (16, 16, 8), (16, 8, 8),
+                     (16, 16, 8), (16, 16, 8), (16, 16, 8), (16, 8, 8),
+                     (8, 8, 8), (8, 16, 8), (8, 16, 8), (8, 8, 8)],
+    # explicit targets, M = 24: per row range both column blocks in pass 1 and again in pass 2
+    ("target", 16): [(16, 16, 8), (16, 8, 8), (16, 16, 8), (16, 8, 8),
+                     (16, 16, 8), (16, 8, 8), (16, 16, 8), (16, 8, 8),
+                     (8, 16, 8), (8, 8, 8), (8, 16, 8), (8, 8, 8)],
+    # topk, M = 40: one pass
+    ("topk", 16): [(16, 16, 8), (16, 16, 8), (16, 8, 8), (16, 16, 8), (16, 16, 8), (16, 8, 8),
+                   (8, 16, 8), (8, 16, 8), (8, 8, 8)],
+    # a single column block is computed once: pass 2 reads it from the scratch
+    ("paired", 64): [(40, 40, 8)], ("target", 64): [(40, 24, 8)], ("topk", 64): [(40, 40, 8)],
+}
+
+
+@pytest.mark.parametrize("block", [16, 64])
+def test_block_walk_gemm_schedule(block, monkeypatch):
+    """The exact ordered list of GEMM calls behind target_ranks and topk (the walk's skip rules), and the results
+    of those calls against numpy on the same integer inputs."""
+    calls = []
+    real = T._gemm_f32
+
+    def recording(*a, **kw):
+        calls.append(tuple(a[:3]))
+        return real(*a, **kw)
+
+    def run(fn):
+        calls.clear()
+        monkeypatch.setattr(T, "_gemm_f32", recording)
+        out = fn()
+        monkeypatch.setattr(T, "_gemm_f32", real)
+        return out, list(calls)
+
+    q, c, target = integer_case(8, 40, 40, seed=21, paired=True)
+    S = q.astype(np.int64) @ c.astype(np.int64).T
+    res, got = run(lambda: EV.target_ranks(cuda(q), cuda(c), block=block))
+    assert got == GEMM_SCHEDULE["paired", block]
+    assert_same(host(res), reference_ranks(S, target))
+
+    top, got = run(lambda: EV.topk(cuda(q), cuda(c), 5, block=block))
+    assert got == GEMM_SCHEDULE["topk", block]
+    order = np.argsort(-S, axis=1, kind="stable")[:, :5]  # equal scores: the lower index first
+    assert np.array_equal(top.indices.cpu().numpy(), order)
+    assert np.array_equal(top.scores.cpu().numpy(), np.take_along_axis(S, order, 1))
+
+    q, c, target = integer_case(8, 40, 24, seed=22)
+    res, got = run(lambda: EV.target_ranks(cuda(q), cuda(c), cuda(target), block=block))
+    assert got == GEMM_SCHEDULE["target", block]
+    assert_same(host(res), reference_ranks(q.astype(np.int64) @ c.astype(np.int64).T, target))
 
 
 # ------------------------------------------------------------------------------ 2. float ranks

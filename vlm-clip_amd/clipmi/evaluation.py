@@ -8,7 +8,9 @@ Two families, both device-resident until one final transfer:
   the [N, M] score matrix (40 GB of fp32 at N = 100k).  Here the scores are walked in ``block x block`` tiles of
   the exact-f32 GEMM (``towers._gemm_f32``, the cosines the contrastive head trains on) and reduced by
   csrc/eval.hip, so scratch is one tile.  ``topk`` keeps each query's k best candidates over the same tiles
-  (csrc/topk.hip): which candidates were retrieved, or with ``exclude`` the hardest negatives.
+  (csrc/topk.hip): which candidates were retrieved, or with ``exclude`` the hardest negatives; ``group_ranks``
+  ranks the best of the candidates that share the query's key (csrc/eval_keys.hip).  All of them are consumers
+  of the one walk, ``_block_walk``, alone or (``evaluate_retrieval`` with keys) together.
 * **Classification** (``ClassificationMeter``, ``classification_report``, ``accuracy``, ``evaluate_model``,
   ``evaluate_enhanced_model``): drop-ins for the reference's ``evaluation.evaluate_model`` (evaluation.py:17-68)
   and ``utils.evaluate_enhanced_model`` (utils.py:24-68) without their four ``.cpu()`` round trips per batch and
@@ -107,6 +109,16 @@ def _block_size(who, block):
     return blk
 
 
+def _exclude_rows(who, exclude, n, dev):
+    """``exclude`` as the kernels read it: int64 [n], contiguous, on the features' device (None stays None)."""
+    if exclude is None:
+        return None
+    ex = torch.as_tensor(exclude)
+    if ex.shape != (n,):
+        raise ValueError(f"{who}: exclude must have shape ({n},), got {tuple(ex.shape)}")
+    return ex.detach().to(device=dev, dtype=torch.int64).contiguous()
+
+
 def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
     """Rank statistics of each query's target among all candidates, scores = query @ candidates.T.
 
@@ -121,7 +133,7 @@ def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
     from it), so the target score is never taken from anywhere else: ties with a duplicate of the target are
     exact.  No host synchronisation; ``RankResult.check()`` reports an out-of-range target."""
     q, c = _score_operands("target_ranks", query, candidates)
-    (N, E), M, dev = q.shape, c.shape[0], q.device
+    N, M, dev = q.shape[0], c.shape[0], q.device
     if target is None:
         if N != M:
             raise ValueError(f"target_ranks: paired data (target=None) needs N == M, got {N} and {M}")
@@ -130,35 +142,9 @@ def target_ranks(query, candidates, target=None, *, block=None) -> RankResult:
         tgt = torch.as_tensor(target).detach().to(device=dev, dtype=torch.int64).contiguous()
         if tgt.shape != (N,):
             raise ValueError(f"target_ranks: target must have shape ({N},), got {tuple(tgt.shape)}")
-    blk = _block_size("target_ranks", block)
-    bm, bn = min(blk, N), min(blk, M)
-    sbuf = torch.empty(bm * bn, dtype=torch.float32, device=dev)
-    res = RankResult(greater=torch.empty(N, dtype=torch.int32, device=dev),
-                     equal=torch.empty(N, dtype=torch.int32, device=dev),
-                     top1=torch.empty(N, dtype=torch.int32, device=dev),
-                     top1_score=torch.empty(N, dtype=torch.float32, device=dev),
-                     target_score=torch.empty(N, dtype=torch.float32, device=dev),
-                     bad=torch.zeros(1, dtype=torch.int32, device=dev))
-    s = T.K.stream()
-    cblocks = [(c0, min(blk, M - c0)) for c0 in range(0, M, blk)]
-
-    def scores(r0, rows, c0, cols):
-        T._gemm_f32(rows, cols, E, q[r0:], E, True, c[c0:], E, True, sbuf, cols)
-
-    for r0 in range(0, N, blk):
-        rows = min(blk, N - r0)
-        for c0, cols in cblocks:
-            if tgt is None and (c0 >= r0 + rows or c0 + cols <= r0):
-                continue  # paired: no t_i = i of these rows lies in these columns
-            scores(r0, rows, c0, cols)
-            call("clipmi_rank_pick", s, P_(sbuf), cols, N, M, r0, rows, c0, cols, P_(tgt), P_(res.target_score),
-                 P_(res.bad))
-        for n, (c0, cols) in enumerate(cblocks):
-            if len(cblocks) > 1:  # a single column block is still in the scratch from the first pass
-                scores(r0, rows, c0, cols)
-            call("clipmi_rank_count", s, P_(sbuf), cols, N, M, r0, rows, c0, cols, P_(tgt), P_(res.target_score),
-                 1 if n == 0 else 0, P_(res.greater), P_(res.equal), P_(res.top1), P_(res.top1_score))
-    return res
+    walk = _RankWalk(N, M, dev, tgt)
+    _block_walk(q, c, _block_size("target_ranks", block), [walk])
+    return walk.res
 
 
 TOPK_MAX = 256  # CLIPMI_TOPK_MAX of include/clipmi.h
@@ -189,29 +175,11 @@ def topk(query, candidates, k, *, exclude=None, block=None) -> TopK:
     k = int(k)
     if not 1 <= k <= TOPK_MAX:
         raise ValueError(f"topk: k must be in [1, {TOPK_MAX}], got {k}")
-    ex = None
-    if exclude is not None:
-        ex = torch.as_tensor(exclude)
-        if query.dim() == 2 and ex.shape != (query.shape[0],):
-            raise ValueError(f"topk: exclude must have shape ({query.shape[0]},), got {tuple(ex.shape)}")
+    ex = _exclude_rows("topk", exclude, query.shape[0], query.device) if query.dim() == 2 else None
     q, c = _score_operands("topk", query, candidates)
-    (N, E), M, dev = q.shape, c.shape[0], q.device
-    if ex is not None:
-        ex = ex.detach().to(device=dev, dtype=torch.int64).contiguous()
-    blk = _block_size("topk", block)
-    bm, bn = min(blk, N), min(blk, M)
-    sbuf = torch.empty(bm * bn, dtype=torch.float32, device=dev)
-    res = TopK(scores=torch.empty(N, k, dtype=torch.float32, device=dev),
-               indices=torch.empty(N, k, dtype=torch.int32, device=dev))
-    s = T.K.stream()
-    for r0 in range(0, N, blk):
-        rows = min(blk, N - r0)
-        for c0 in range(0, M, blk):
-            cols = min(blk, M - c0)
-            T._gemm_f32(rows, cols, E, q[r0:], E, True, c[c0:], E, True, sbuf, cols)
-            call("clipmi_topk_merge", s, P_(sbuf), cols, N, M, r0, rows, c0, cols, k, 1 if c0 == 0 else 0, P_(ex),
-                 P_(res.scores), P_(res.indices))
-    return res
+    walk = _TopKWalk(q.shape[0], c.shape[0], q.device, k, ex)
+    _block_walk(q, c, _block_size("topk", block), [walk])
+    return walk.res
 
 
 _topk = topk  # evaluate_retrieval's `topk` keyword shadows the function
@@ -323,16 +291,20 @@ class _TopKWalk:
 
 
 def _block_walk(q, c, blk, consumers):
-    """The shared block walk: every ``blk x blk`` score block of q @ c.T is computed once per pass by the one
-    exact-f32 GEMM call ``target_ranks`` and ``topk`` issue for it, and handed to every consumer.  Per row range,
-    pass 1 (the picks) visits the column blocks some consumer wants, pass 2 (the counts and the top-k merge) all
-    of them; a block that is still in the scratch from pass 1 (a single column block) is not computed again.  So
-    the walk costs at most 2 x (row blocks x column blocks) GEMMs however many consumers ride on it, and every
-    consumer sees the score bits it would have seen alone."""
+    """The block walk every retrieval entry point rides: each ``blk x blk`` score block of q @ c.T is computed once
+    per pass by the exact-f32 GEMM (this function holds the file's one call of it and its one scratch, of one
+    block) and handed to every consumer.  Per row range, pass 1 (the picks) visits the column blocks some consumer
+    wants (paired ranks: those that overlap the row range; a walk without picks, ``topk``'s, has no pass 1), pass 2
+    (the counts and the top-k merge) all of them; a block that is still in the scratch from pass 1 (a single column
+    block) is not computed again.  So the walk costs at most 2 x (row blocks x column blocks) GEMMs however many
+    consumers ride on it, and every consumer sees the score bits it sees alone."""
     (N, E), M = q.shape, c.shape[0]
-    bm, bn = min(blk, N), min(blk, M)
-    sbuf = torch.empty(bm * bn, dtype=torch.float32, device=q.device)
+    sbuf = torch.empty(min(blk, N) * min(blk, M), dtype=torch.float32, device=q.device)
     s = T.K.stream()
+
+    def scores(r0, rows, c0, cols):
+        T._gemm_f32(rows, cols, E, q[r0:], E, True, c[c0:], E, True, sbuf, cols)
+
     cblocks = [(c0, min(blk, M - c0)) for c0 in range(0, M, blk)]
     pickers = [u for u in consumers if u.first_pass is not None]
     for r0 in range(0, N, blk):
@@ -342,13 +314,13 @@ def _block_walk(q, c, blk, consumers):
             users = [u for u in pickers if u.wants(r0, rows, c0, cols)]
             if not users:
                 continue
-            T._gemm_f32(rows, cols, E, q[r0:], E, True, c[c0:], E, True, sbuf, cols)
+            scores(r0, rows, c0, cols)
             held = c0
             for u in users:
                 u.first_pass(s, sbuf, r0, rows, c0, cols, 1 if n == 0 else 0)
         for n, (c0, cols) in enumerate(cblocks):
             if held != c0 or len(cblocks) > 1:
-                T._gemm_f32(rows, cols, E, q[r0:], E, True, c[c0:], E, True, sbuf, cols)
+                scores(r0, rows, c0, cols)
             for u in consumers:
                 u.second_pass(s, sbuf, r0, rows, c0, cols, 1 if n == 0 else 0)
 
@@ -374,15 +346,10 @@ def group_ranks(query, candidates, query_keys, candidate_keys, *, exclude=None, 
     if N >= 0 and M >= 0:
         qk = _host_keys("group_ranks", "query_keys", query_keys, N)
         ck = _host_keys("group_ranks", "candidate_keys", candidate_keys, M)
-        if exclude is not None:
-            ex = torch.as_tensor(exclude)
-            if ex.shape != (N,):
-                raise ValueError(f"group_ranks: exclude must have shape ({N},), got {tuple(ex.shape)}")
+        ex = _exclude_rows("group_ranks", exclude, N, query.device)
     q, c = _score_operands("group_ranks", query, candidates)
     dev = q.device
     blk = _block_size("group_ranks", block)
-    if ex is not None:
-        ex = ex.detach().to(device=dev, dtype=torch.int64).contiguous()
     walk = _GroupWalk(N, M, dev, _device_keys(qk, dev), _device_keys(ck, dev), ex)
     _block_walk(q, c, blk, [walk])
     return walk.res

@@ -26,12 +26,6 @@
 
 namespace {
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // logits = exp(ls) * S (written to L); lse[i]; winv[i] = 1 / |P_i|; ce[i] = lse[i] - winv[i] * sum_{P_i} L[i][j]
 __global__ __launch_bounds__(256) void cek_fwd_kernel(const float* S, float* L, const float* logit_scale,
                                                       const int64_t* keys_all, int B, int Bg, int label0,
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(256) void cek_fwd_kernel(const float* S, float* L, 
   for (int j = lane; j < Bg; j += 64) sum += expf(l[j] - mx);
   sum = wave_sum(sum);
   psum = wave_sum(psum);
-  cnt = wave_sum_i(cnt);
+  cnt = wave_sum(cnt);
   if (lane == 0) {
     const float lse = mx + logf(sum);
     const float w = 1.f / (float)cnt;
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(256) void cek_fwd_chunk_kernel(const float* S, cons
   for (int j = lane; j < C; j += 64) sum += expf(fmaf(s[j], sc, -mx));
   sum = wave_sum(sum);
   psum = wave_sum(psum);
-  cnt = wave_sum_i(cnt);
+  cnt = wave_sum(cnt);
   if (lane == 0) {
     float* r = run + 4 * (int64_t)row;
     if (col0 == 0) {

@@ -17,34 +17,13 @@
 // All fp32 / int32 / int64, no allocation, no synchronisation; an out-of-range target or label raises a
 // device flag (the Python mirror turns it into IndexError) instead of being read.
 #include <algorithm>
-#include "common.h"
+#include "eval_common.h"
 #include "internal.h"
 
 namespace {
 
-constexpr int ET = 256;           // threads per workgroup
-constexpr int WIDE_COLS = 1024;   // wider blocks: one workgroup per row instead of one wave
-constexpr int HIST_MAXC = 64;     // confusion tallies combine in LDS up to C = 64 (16 KiB of int32)
-
-// a row's best score so far: the largest, lowest candidate index on ties; idx < 0 = none yet
-struct Best { float s; int i; };
-__device__ __forceinline__ bool better(float s, int i, const Best& b) {
-  return i >= 0 && (b.i < 0 || s > b.s || (s == b.s && i < b.i));
-}
-__device__ __forceinline__ Best wave_best(Best b) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float s = __shfl_xor(b.s, o, 64);
-    const int i = __shfl_xor(b.i, o, 64);
-    if (better(s, i, b)) { b.s = s; b.i = i; }
-  }
-  return b;
-}
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+constexpr int ET = 256;        // threads per workgroup
+constexpr int HIST_MAXC = 64;  // confusion tallies combine in LDS up to C = 64 (16 KiB of int32)
 
 // target index of global query row i, or -1 when out of [0, M)
 __device__ __forceinline__ int64_t target_of(const int64_t* target, int64_t i, int M) {
@@ -126,51 +105,34 @@ __device__ __forceinline__ void mark_bad_row(int64_t i, int first, int* greater,
   top1_score[i] = -1.f;
 }
 
-// pass 2, one wave per row (4 rows per workgroup)
-template <bool VEC>
-__global__ __launch_bounds__(ET) void rank_count_wave_kernel(const float* S, int64_t lds, int rows, int cols, int row0,
-                                                             int col0, const int64_t* target, int M,
-                                                             const float* target_score, int first, int* greater,
-                                                             int* equal, int* top1, float* top1_score) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * (ET / 64) + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const int64_t i = (int64_t)row0 + r;
-  const int64_t t = target_of(target, i, M);
-  if (t < 0) {
-    if (lane == 0) mark_bad_row(i, first, greater, equal, top1, top1_score);
-    return;
-  }
-  Tally a = tally_row<VEC>(S + (int64_t)r * lds, cols, col0, target_score[i], (int)t, lane, 64);
-  a.gt = wave_isum(a.gt);
-  a.eq = wave_isum(a.eq);
-  a.b = wave_best(a.b);
-  if (lane == 0) merge_row(a, i, first, greater, equal, top1, top1_score);
-}
-
-// pass 2, one workgroup per row (wide blocks)
-template <bool VEC>
-__global__ __launch_bounds__(ET) void rank_count_wg_kernel(const float* S, int64_t lds, int rows, int cols, int row0,
-                                                           int col0, const int64_t* target, int M,
-                                                           const float* target_score, int first, int* greater,
-                                                           int* equal, int* top1, float* top1_score) {
-  __shared__ Tally part[ET / 64];
+// pass 2.  WAVES = 1: one wave per row, 4 rows per workgroup; WAVES = 4: one workgroup per row (wide blocks), its
+// waves' tallies combined in LDS
+template <int WAVES, bool VEC>
+__global__ __launch_bounds__(ET) void rank_count_kernel(const float* S, int64_t lds, int rows, int cols, int row0,
+                                                        int col0, const int64_t* target, int M,
+                                                        const float* target_score, int first, int* greater, int* equal,
+                                                        int* top1, float* top1_score) {
+  __shared__ Tally part[WAVES];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = blockIdx.x;
+  const int r = WAVES == 1 ? blockIdx.x * (ET / 64) + w : blockIdx.x;
+  if (WAVES == 1 && r >= rows) return;  // its waves share no barrier; the wide grid is exact
+  const int tid = WAVES == 1 ? lane : (int)threadIdx.x;
   const int64_t i = (int64_t)row0 + r;
-  const int64_t t = target_of(target, i, M);  // uniform over the workgroup
+  const int64_t t = target_of(target, i, M);  // uniform over the row's threads
   if (t < 0) {
-    if (threadIdx.x == 0) mark_bad_row(i, first, greater, equal, top1, top1_score);
+    if (tid == 0) mark_bad_row(i, first, greater, equal, top1, top1_score);
     return;
   }
-  Tally a = tally_row<VEC>(S + (int64_t)r * lds, cols, col0, target_score[i], (int)t, threadIdx.x, ET);
-  a.gt = wave_isum(a.gt);
-  a.eq = wave_isum(a.eq);
+  Tally a = tally_row<VEC>(S + (int64_t)r * lds, cols, col0, target_score[i], (int)t, tid, WAVES * 64);
+  a.gt = wave_sum(a.gt);
+  a.eq = wave_sum(a.eq);
   a.b = wave_best(a.b);
-  if (lane == 0) part[w] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < ET / 64; ++k) {
+  if (WAVES > 1) {
+    if (lane == 0) part[w] = a;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    for (int k = 1; k < WAVES; ++k) {
       a.gt += part[k].gt;
       a.eq += part[k].eq;
       if (better(part[k].b.s, part[k].b.i, a.b)) a.b = part[k].b;
@@ -255,11 +217,11 @@ extern "C" int clipmi_rank_count(void* stream, const float* S, int64_t lds, int 
   const bool vec = block_vec_ok(S, lds);
   const hipStream_t s = (hipStream_t)stream;
   if (cols > WIDE_COLS) {
-    auto k = vec ? rank_count_wg_kernel<true> : rank_count_wg_kernel<false>;
+    auto k = vec ? rank_count_kernel<4, true> : rank_count_kernel<4, false>;
     hipLaunchKernelGGL(k, dim3(rows), dim3(ET), 0, s, S, lds, rows, cols, row0, col0, target, M, target_score, first,
                        greater, equal, top1, top1_score);
   } else {
-    auto k = vec ? rank_count_wave_kernel<true> : rank_count_wave_kernel<false>;
+    auto k = vec ? rank_count_kernel<1, true> : rank_count_kernel<1, false>;
     hipLaunchKernelGGL(k, dim3((rows + ET / 64 - 1) / (ET / 64)), dim3(ET), 0, s, S, lds, rows, cols, row0, col0, target,
                        M, target_score, first, greater, equal, top1, top1_score);
   }

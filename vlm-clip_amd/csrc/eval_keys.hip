@@ -21,34 +21,13 @@
 //
 // topk_hits turns the candidate lists of topk.hip into relevance prefix counts (precision@k, average precision):
 // one wave per row, ballot and popcount.
-#include "common.h"
+#include "eval_common.h"
 #include "internal.h"
 
 namespace {
 
-constexpr int GT = 256;          // threads per workgroup (4 waves)
-constexpr int R = 16;            // rows per strip
-constexpr int WIDE_COLS = 1024;  // wider blocks: one workgroup per strip instead of one wave (as eval.hip)
-
-struct Best { float s; int i; };
-// as better() of eval.hip: the larger score, the lower candidate index on equal scores; idx < 0 = none
-__device__ __forceinline__ bool better(float s, int i, const Best& b) {
-  return i >= 0 && (b.i < 0 || s > b.s || (s == b.s && i < b.i));
-}
-__device__ __forceinline__ Best wave_best(Best b) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float s = __shfl_xor(b.s, o, 64);
-    const int i = __shfl_xor(b.i, o, 64);
-    if (better(s, i, b)) { b.s = s; b.i = i; }
-  }
-  return b;
-}
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+constexpr int GT = 256;  // threads per workgroup (4 waves)
+constexpr int R = 16;    // rows per strip
 
 // a thread's tallies of one row.  COUNT = false (pick): a = positives seen, best = the best positive.
 // COUNT = true: a / b = negatives above / equal to the row's pos_score, best = the row maximum.
@@ -187,8 +166,8 @@ __global__ __launch_bounds__(GT) void group_strip_kernel(const Args p) {
 
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    t[r].a = wave_isum(t[r].a);
-    if (COUNT) t[r].b = wave_isum(t[r].b);
+    t[r].a = wave_sum(t[r].a);
+    if (COUNT) t[r].b = wave_sum(t[r].b);
     t[r].best = wave_best(t[r].best);
   }
   if (WAVES == 1) {
@@ -214,6 +193,12 @@ __global__ __launch_bounds__(GT) void group_strip_kernel(const Args p) {
       merge_row<COUNT>(p, a, (int64_t)p.row0 + r0 + r);
     }
   }
+}
+
+// the fields both passes read, in Args' order; the pass's own pointers start null
+Args block_args(const float* S, int64_t lds, int M, int row0, int rows, int col0, int cols, const int64_t* qkeys,
+                const int64_t* ckeys, const int64_t* exclude, int first) {
+  return Args{S, lds, rows, cols, row0, col0, M, first, qkeys, ckeys, exclude};
 }
 
 template <bool COUNT>
@@ -259,9 +244,7 @@ extern "C" int clipmi_group_pick(void* stream, const float* S, int64_t lds, int 
   CLIPMI_TRY(check_block(__func__, S, lds, N, M, row0, rows, col0, cols));
   CLIPMI_REQUIRE(qkeys && ckeys, "null keys");
   CLIPMI_REQUIRE(pos_score && pos_idx && n_pos, "null output");
-  Args p{};
-  p.S = S, p.lds = lds, p.rows = rows, p.cols = cols, p.row0 = row0, p.col0 = col0, p.M = M, p.first = first;
-  p.qkeys = qkeys, p.ckeys = ckeys, p.exclude = exclude;
+  Args p = block_args(S, lds, M, row0, rows, col0, cols, qkeys, ckeys, exclude, first);
   p.pos_score = pos_score, p.pos_idx = pos_idx, p.n_pos = n_pos;
   launch_strips<false>((hipStream_t)stream, p);
   CLIPMI_CHECK_LAUNCH();
@@ -276,9 +259,7 @@ extern "C" int clipmi_group_count(void* stream, const float* S, int64_t lds, int
   CLIPMI_REQUIRE(qkeys && ckeys, "null keys");
   CLIPMI_REQUIRE(pos_score && n_pos, "null input");
   CLIPMI_REQUIRE(greater && equal && top1 && top1_score, "null output");
-  Args p{};
-  p.S = S, p.lds = lds, p.rows = rows, p.cols = cols, p.row0 = row0, p.col0 = col0, p.M = M, p.first = first;
-  p.qkeys = qkeys, p.ckeys = ckeys, p.exclude = exclude;
+  Args p = block_args(S, lds, M, row0, rows, col0, cols, qkeys, ckeys, exclude, first);
   p.pos_score = const_cast<float*>(pos_score), p.n_pos = const_cast<int*>(n_pos);
   p.greater = greater, p.equal = equal, p.top1 = top1, p.top1_score = top1_score;
   launch_strips<true>((hipStream_t)stream, p);

@@ -19,14 +19,13 @@
 // sorted once.  A row that gained nothing is not sorted or written back.  LDS is 4 P keys per workgroup (4 KiB at
 // k <= 64, 16 KiB at k = 256).  A row has one owner per launch and the blocks of a row range are serialised on
 // the stream: no atomics, no allocation, no synchronisation.
-#include "common.h"
+#include "eval_common.h"
 #include "internal.h"
 
 namespace {
 
-constexpr int TT = 256;          // threads per workgroup (4 waves)
-constexpr int WIDE_COLS = 1024;  // wider blocks: one workgroup per row instead of one wave (as eval.hip)
-constexpr int UNROLL = 2;        // 16-B loads in flight per lane and step
+constexpr int TT = 256;    // threads per workgroup (4 waves)
+constexpr int UNROLL = 2;  // 16-B loads in flight per lane and step
 
 typedef unsigned long long tkey;
 
