@@ -73,7 +73,10 @@ typedef struct clipmi_gemm_desc {
   int split_k;
   void* workspace; int64_t workspace_bytes;
   float* bias_grad;     /* wgrad only: bias_grad[m] += sum_k A(m,k) (fused Linear bias gradient, fp32) */
-  int force_small_tile; /* 1: 128x128 register-staged kernel; >=2: 256-kernel schedule variant (bench) */
+  int force_small_tile; /* kernel override for tests and bench tools; 0: the production rule.  1: the 128x128
+                         * register-staged kernel; other codes name a schedule (4, 9, 28, 32, 1xx; 40 / 41 with MXFP8
+                         * operands): the one decode table is gemm_force() in csrc/gemm_plan.cpp, the names in
+                         * clipmi/_lib.py (FORCE_*).  clipmi_gemm_plan() reports what a descriptor selects. */
   /* ab_dtype == CLIPMI_FP8 (BASELINE config 5, forward GEMMs of the frozen towers): A, B are OCP e4m3
    * bytes, both k-major, K % 128 == 0; a_scale / b_scale are E8M0 bytes [rows][K/32] (OCP MX:
    * element value = fp8 * 2^(scale - 127)); v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulation,
@@ -110,6 +113,22 @@ typedef struct clipmi_gemm_desc {
 int64_t clipmi_gemm_split3_ws(int M, int N, int K, int a_kmajor, int b_kmajor, int split_k);
 
 int clipmi_gemm(void* stream, const clipmi_gemm_desc* d);
+/* The kernel selection of clipmi_gemm (x3out 0) or clipmi_gemm_x3out (x3out != 0) for d, without launching
+ * anything (clipmi_version() >= 10): the same validation and the same plan the launch uses, so the same errors.
+ * Operand pointers are read for null-ness and alignment only; no GPU is needed.  Strings are static. */
+typedef struct clipmi_gemm_plan_info {
+  const char* kernel; /* "none" (M or N == 0), "f32", "bf16_128", "pp8", "asm8", "w4p", "w4p_pf", "fp8_8w", "fp8_w4p";
+                       * "experiment" in a CLIPMI_GEMM_EXPERIMENTS build's extra schedules */
+  const char* label;  /* the live profiler's label of the launch (clipmi_prof_*; bench.py's families) */
+  int tile, tiles_n, ntiles; /* tile edge; column tiles; tiles */
+  int splits, k_per_split;   /* effective split-K count and each split's k range */
+  int raster;                /* tile-rows per raster group (0: row-major) */
+  int stagger;               /* first-round stagger of "pp8" (force 1xx), else 0 */
+  int specialised;           /* the epilogue is a compile-time instance (0: the runtime-flag instance) */
+  int bias_grad;             /* the fused bias-gradient instance */
+  int reduce;                /* split-K second stage: 0 none, 1 the 16-byte form (deferrable), 2 the scalar form */
+} clipmi_gemm_plan_info;
+int clipmi_gemm_plan(const clipmi_gemm_desc* d, int x3out, clipmi_gemm_plan_info* out);
 /* Strided batch of nb1 x nb2 fp32 products (exact f32; flags: beta only): product z = i1 * nb2 + i2 reads
  * A + i1 * sa1 + i2 * sa2, B + i1 * sb1 + i2 * sb2 and writes C + i1 * sc1 + i2 * sc2 (elements), the
  * rest as clipmi_gemm.  One launch for the per-(sample, head) score / context products of attention at

@@ -12,6 +12,8 @@ import torch
 
 # epilogue flags of include/clipmi.h (plain numbers: this module does not load the library)
 EPI_BIAS, EPI_QGELU, EPI_RESID, EPI_BETA, EPI_STORE_PRE, EPI_MUL_AUX = 1, 2, 8, 64, 128, 512
+# kernel overrides (clipmi/_lib.py FORCE_*; 11 is an experiments-build schedule, the ping-pong kernel otherwise)
+FORCE_RULE, FORCE_128, FORCE_ASM8, FORCE_PP8, FORCE_W4P, FORCE_W4P_PF = 0, 1, 4, 9, 28, 32
 
 GUARD_BYTES = 4096
 GUARD_PATTERN = 0xFF  # 0xFFFF / 0xFFFFFFFF are NaNs in bf16 / fp32: an output element nobody stored fails its compare
@@ -161,11 +163,11 @@ def gemm_cases():
     i = 0
     for (M, N, K) in GEMM_SHAPES + [(264, 136, 192)]:  # the last: ragged, every layout, the 256-tile kernels
         for (akm, bkm) in LAYOUTS:
-            variants = [0, 1, 4, 11]
+            variants = [FORCE_RULE, FORCE_128, FORCE_ASM8, 11]
             if akm and _takes_256(M, N, K):
-                variants += [9, 28, 32]
+                variants += [FORCE_PP8, FORCE_W4P, FORCE_W4P_PF]
             if not akm and not bkm:
-                variants += [28]
+                variants += [FORCE_W4P]
             for v in variants:
                 cases.append(GemmCase(M, N, K, akm, bkm, c=("f32", "bf16")[i % 2], small=v))
                 i += 1
@@ -177,7 +179,7 @@ def gemm_cases():
         for (akm, bkm) in (LAYOUTS[0], LAYOUTS[1 + j % 3]):
             cases.append(GemmCase(M, N, K, akm, bkm, ab="x3"))
     # 3. Every exact epilogue in every alignment class; ldc, ldr and ldaux all differ.
-    v256 = [0, 9, 28, 32, 11, 4, 0]
+    v256 = [FORCE_RULE, FORCE_PP8, FORCE_W4P, FORCE_W4P_PF, 11, FORCE_ASM8, FORCE_RULE]
     for e, (flags, bias, alpha) in enumerate(EXACT_EPILOGUES):
         kw = dict(flags=flags, bias=bias, alpha=alpha)
         # vec8: bf16 C, N % 8 == 0, pads of 8 / 16 / 24 -- the 128-tile kernel and a 256-tile variant
@@ -202,17 +204,17 @@ def gemm_cases():
     # 4. lda / ldb = the row length + 8, every layout (contiguous C: "vec8" / "vec")
     for j, (akm, bkm) in enumerate(LAYOUTS):
         for (M, N, K) in ((256, 256, 128), (200, 136, 72)):
-            cases.append(GemmCase(M, N, K, akm, bkm, c=("bf16", "f32")[j % 2], small=(0, 11, 4, 28)[j], pad_ab=8))
+            cases.append(GemmCase(M, N, K, akm, bkm, c=("bf16", "f32")[j % 2], small=(FORCE_RULE, 11, FORCE_ASM8, FORCE_W4P)[j], pad_ab=8))
             cases.append(GemmCase(M, N, K, akm, bkm, ab="f32", pad_ab=8))
     # 5. split-K on the weight-gradient layout with beta (fp32 C): splits 1 / 3 / 8, the 8-wave (4) and persistent
     #    4-wave (28) kernels, a ragged 264x136 output; "vec" (deferred vector reduce) and "scalar" (ldc = N + 1: the
     #    scalar reduce kernel); the fused bias gradient where the 256-tile kernel takes it
     for (M, N, K) in ((256, 256, 128), (264, 136, 200), (768, 256, 4160)):
         for split in (1, 3, 8):
-            for v in (4, 28):
+            for v in (FORCE_ASM8, FORCE_W4P):
                 cases.append(GemmCase(M, N, K, False, False, small=v, flags=EPI_BETA, split=split,
                                       ldc=(0, 1, 4)[(split + v) % 3]))
-            cases.append(GemmCase(M, N, K, False, False, small=(4, 28, 0)[split % 3], flags=EPI_BETA, split=split,
+            cases.append(GemmCase(M, N, K, False, False, small=(FORCE_ASM8, FORCE_W4P, FORCE_RULE)[split % 3], flags=EPI_BETA, split=split,
                                   bias_grad=True))
         cases.append(GemmCase(M, N, K, False, False, ab="f32", flags=EPI_BETA, split=3))
         cases.append(GemmCase(M, N, K, False, False, ab="x3", flags=EPI_BETA, split=3))

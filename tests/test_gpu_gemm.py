@@ -45,7 +45,7 @@ def _ref_epi(acc, flags, bias=None, aux=None, res=None, cold=None, alpha=1.0):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("akm,bkm", [(True, True), (True, False), (False, True), (False, False)])
 # production schedule, 128 tile, single-group 256, half-tile pipeline
-@pytest.mark.parametrize("small", [0, 1, 4, 11])
+@pytest.mark.parametrize("small", [_lib.FORCE_RULE, _lib.FORCE_128, _lib.FORCE_ASM8, 11])
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (200, 136, 72), (77, 64, 768), (1000, 512, 200),
                                    (1000, 776, 768), (600, 264, 1000), (512, 256, 64), (520, 384, 96),
                                    (768, 256, 4160)])
@@ -151,7 +151,7 @@ def _mx8_exact(R, K, seed):
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (300, 520, 256), (1024, 768, 1024), (77, 64, 640),
                                    (256, 256, 384), (2304, 1280, 4096), (1000, 1100, 768), (4096, 512, 2048)])
-@pytest.mark.parametrize("variant", [0, 40, 41])
+@pytest.mark.parametrize("variant", [_lib.FORCE_RULE, _lib.FORCE_FP8_8W, _lib.FORCE_FP8_RULE])
 def test_gemm_fp8_block_scaled_exact(M, N, K, variant):
     """v_mfma_scale_f32_32x32x64_f8f6f4 GEMMs (0: production dispatch; 40: the 8-wave kernel everywhere;
     41: the persistent 4-wave kernel wherever K % 256 == 0 and M, N >= 256): integer operands and power-of-two
@@ -166,7 +166,7 @@ def test_gemm_fp8_block_scaled_exact(M, N, K, variant):
 
 
 @pytest.mark.parametrize("flags", [0, _lib.EPI_BIAS, _lib.EPI_BIAS | _lib.EPI_RESID, _lib.EPI_BIAS | _lib.EPI_QGELU])
-@pytest.mark.parametrize("variant", [0, 40, 41])
+@pytest.mark.parametrize("variant", [_lib.FORCE_RULE, _lib.FORCE_FP8_8W, _lib.FORCE_FP8_RULE])
 def test_gemm_fp8_epilogues(flags, variant):
     M, N, K = 600, 384, 512
     x = _mk((M, K), torch.bfloat16, 21)
@@ -215,7 +215,7 @@ def _mx_close(m, ref, frac=0.99):
     assert (err <= 0).all(), err.max().item()
 
 
-@pytest.mark.parametrize("variant", [0, 40, 41])
+@pytest.mark.parametrize("variant", [_lib.FORCE_RULE, _lib.FORCE_FP8_8W, _lib.FORCE_FP8_RULE])
 def test_gemm_fp8_mxfp8_output(variant):
     """fc1's fused epilogue in the fp8 towers: bias + quick_gelu, written as MXFP8 [M, N] + scales."""
     M, N, K = 600, 512, 512
@@ -256,7 +256,7 @@ def test_layernorm_mxfp8(R, D):
     assert torch.allclose(mean, x.float().mean(1), atol=1e-4)
 
 
-@pytest.mark.parametrize("var", [28, 32])
+@pytest.mark.parametrize("var", [_lib.FORCE_W4P, _lib.FORCE_W4P_PF])
 @pytest.mark.parametrize("bkm,flags", [
     (True, _lib.EPI_BIAS), (True, _lib.EPI_BIAS | _lib.EPI_RESID),
     (True, _lib.EPI_BIAS | _lib.EPI_QGELU | _lib.EPI_STORE_PRE), (True, _lib.EPI_BIAS | _lib.EPI_QGELU), (True, 0),
@@ -276,7 +276,7 @@ def test_gemm_4wave_matches_pingpong(var, bkm, flags, M, N, K):
     res = _mk((M, N), torch.bfloat16, 14)
     aux0 = _mk((M, N), torch.bfloat16, 15)
     outs = []
-    for v in (9, var):
+    for v in (_lib.FORCE_PP8, var):
         C = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
         aux = aux0.clone()
         kern.gemm(M, N, K, A, K, True, B, B.stride(0), bkm, C, N, bias=bias, residual=res, ldr=N, aux=aux, ldaux=N,
@@ -294,7 +294,7 @@ def test_gemm_4wave_matches_pingpong(var, bkm, flags, M, N, K):
                                               (20000, 2304, 768, 4), (300, 768, 768, 3), (4100, 520, 264, 2),
                                               (9000, 768, 768, 1)])
 @pytest.mark.parametrize("bias", [False, True])
-@pytest.mark.parametrize("var", [28])
+@pytest.mark.parametrize("var", [_lib.FORCE_W4P])
 def test_wgrad_4wave_matches_8wave(T, Nout, Kin, split, bias, var):
     """Weight gradient on the persistent 4-wave kernel (gemm4.hip, variant 28) vs the 8-wave wgrad
     kernel (variant 4): the same k order of MFMA accumulation per output element, so bitwise-equal
@@ -304,7 +304,7 @@ def test_wgrad_4wave_matches_8wave(T, Nout, Kin, split, bias, var):
     C0 = _mk((Nout, Kin), torch.float32, 23)
     db0 = _mk((Nout,), torch.float32, 24)
     outs = []
-    for v in (4, var):
+    for v in (_lib.FORCE_ASM8, var):
         C, db = C0.clone(), db0.clone()
         ws = torch.empty(max(1, split) * Nout * (Kin + 1), device="cuda", dtype=torch.float32)
         kern.gemm(Nout, Kin, T, dY, Nout, False, X, Kin, False, C, Kin, flags=_lib.EPI_BETA, split_k=split,
@@ -319,7 +319,7 @@ def test_wgrad_4wave_matches_8wave(T, Nout, Kin, split, bias, var):
 
 
 @pytest.mark.parametrize("raster", ["0", "4", "8"])
-@pytest.mark.parametrize("var", [9, 28])
+@pytest.mark.parametrize("var", [_lib.FORCE_PP8, _lib.FORCE_W4P])
 def test_gemm_raster_groups_bitwise(raster, var, monkeypatch):
     """CLIPMI_RASTER (tile-rows per rasterisation group) only reorders the tiles: every output
     element keeps its k order, so the result is bitwise equal to row-major order (both the 8-wave
@@ -390,3 +390,97 @@ def test_gemm_split3_rejects_bad_workspace_and_bias_grad():
         kern.gemm(256, 256, 256, A, 256, True, B, 256, True, C, 256, flags=_lib.GEMM_SPLIT3,
                   workspace=torch.empty(1024, dtype=torch.uint8, device="cuda"))
 
+
+
+# ------------------------------------------------------------------ the plan query against what ran
+def _plan_case(name):
+    """-> (descriptor, tensors kept alive, output tensor, fp32 reference, relative bound).  Bounds: this file's
+    (2e-2 plain bf16 products, 3e-2 bf16 / 1e-2 fp32 epilogues, 1e-2 weight gradients, exact integer MXFP8)."""
+    from clipmi._lib import BF16, F32, FP8, GemmDesc
+    d = GemmDesc()
+    d.alpha, d.split_k, d.bias_dtype = 1.0, 1, F32
+    keep = []
+    if name.startswith("fp8"):
+        M, N, K = 256, 256, int(name.split("_k")[1])
+        A, B = _mx8_exact(M, K, 1), _mx8_exact(N, K, 2)
+        C = torch.empty(M, N, device="cuda", dtype=torch.float32)
+        d.M, d.N, d.K = M, N, K
+        d.A, d.lda, d.a_kmajor, d.B, d.ldb, d.b_kmajor = A.q.data_ptr(), K, 1, B.q.data_ptr(), K, 1
+        d.a_scale, d.b_scale = A.s.data_ptr(), B.s.data_ptr()
+        d.C, d.ldc, d.ab_dtype, d.c_dtype = C.data_ptr(), N, FP8, F32
+        return d, [A, B], C, A.dequant() @ B.dequant().t(), 0.0
+    if name.startswith("wgrad"):
+        T, M, N = 128, 256, 256
+        split, bias = (2, True) if name == "wgrad_split2_bias" else (1, False)
+        dY, X = _mk((T, M), torch.bfloat16, 9), _mk((T, N), torch.bfloat16, 10)
+        C = _mk((M, N), torch.float32, 11)
+        ref = C + dY.float().t() @ X.float()
+        d.M, d.N, d.K = M, N, T
+        d.A, d.lda, d.B, d.ldb = dY.data_ptr(), M, X.data_ptr(), N
+        d.C, d.ldc, d.ab_dtype, d.c_dtype, d.flags, d.split_k = C.data_ptr(), N, BF16, F32, _lib.EPI_BETA, split
+        if split > 1:
+            ws = torch.empty(split * M * (N + 1), device="cuda", dtype=torch.float32)
+            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+            keep.append(ws)
+        if bias:
+            db = torch.zeros(M, device="cuda", dtype=torch.float32)
+            d.bias_grad = db.data_ptr()
+            keep.append(db)
+        return d, keep + [dY, X], C, ref, 1e-2
+    M, N, K, bkm, flags, cdt = {
+        "fwd_bias_k64": (256, 256, 64, True, _lib.EPI_BIAS, torch.bfloat16),
+        "fwd_bias_k1536": (256, 256, 1536, True, _lib.EPI_BIAS, torch.bfloat16),
+        "fwd_bias_resid_f32_k1536": (256, 256, 1536, True, _lib.EPI_BIAS | _lib.EPI_RESID, torch.float32),
+        "fwd_bias_small": (248, 120, 64, True, _lib.EPI_BIAS, torch.bfloat16),
+        "fwd_bias_gelu": (256, 256, 64, True, _lib.EPI_BIAS | _lib.EPI_GELU, torch.bfloat16),
+        "dgrad_mulaux_k64": (256, 256, 64, False, _lib.EPI_MUL_AUX, torch.bfloat16),
+        "dgrad_k1536": (256, 256, 1536, False, 0, torch.bfloat16),
+    }[name]
+    A = _mk((M, K), torch.bfloat16, 3) * 0.25
+    B = _mk((N, K) if bkm else (K, N), torch.bfloat16, 4) * 0.25
+    bias, aux, res = _mk((N,), torch.float32, 5), _mk((M, N), cdt, 6), _mk((M, N), cdt, 7)
+    C = torch.empty(M, N, device="cuda", dtype=cdt)
+    d.M, d.N, d.K = M, N, K
+    d.A, d.lda, d.a_kmajor = A.data_ptr(), K, 1
+    d.B, d.ldb, d.b_kmajor = B.data_ptr(), B.stride(0), int(bkm)
+    d.C, d.ldc, d.ab_dtype, d.c_dtype, d.flags = C.data_ptr(), N, BF16, (BF16 if cdt == torch.bfloat16 else F32), flags
+    d.bias, d.residual, d.ldr, d.aux, d.ldaux = bias.data_ptr(), res.data_ptr(), N, aux.data_ptr(), N
+    acc = A.float() @ (B.float().t() if bkm else B.float())
+    ref, _ = _ref_epi(acc, flags, bias, aux, res)
+    return d, [A, B, bias, aux, res], C, ref, (3e-2 if cdt == torch.bfloat16 else 1e-2)
+
+
+_PLAN_WANT = {  # kernel, label: the production rule at these shapes (tests/test_cpu_gemm_plan.py pins the rule itself)
+    "fwd_bias_k64": ("pp8", "gemm256_fwd_bias"), "fwd_bias_k1536": ("w4p", "gemm256_fwd_bias"),
+    "fwd_bias_resid_f32_k1536": ("w4p", "gemm256_fwd_bias_resid_f32"), "fwd_bias_small": ("bf16_128", "gemm_fwd_bias"),
+    "fwd_bias_gelu": ("bf16_128", "gemm_fwd_bias_gelu"), "dgrad_mulaux_k64": ("w4p_pf", "gemm256_dgrad_mulaux"),
+    "dgrad_k1536": ("w4p", "gemm256_dgrad"), "wgrad_split2_bias": ("w4p", "gemm256_wgrad_splitk"),
+    "wgrad_beta": ("w4p", "gemm256_wgrad"), "fp8_k256": ("fp8_w4p", "gemm_fp8"), "fp8_k128": ("fp8_8w", "gemm_fp8"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_PLAN_WANT))
+def test_launch_records_the_planned_label(name):
+    """clipmi_gemm_plan() against what ran: with the live profiler armed for every label a plan can carry, the one
+    launch records exactly the label the query reports for the same descriptor, and its output matches torch."""
+    import ctypes
+    import test_cpu_gemm_plan as TP
+    L = _lib.lib()
+    d, keep, C, ref, tol = _plan_case(name)
+    p = _lib.gemm_plan(d)
+    assert (p["kernel"], p["label"]) == _PLAN_WANT[name]
+    labels = sorted({l for ls in TP._bench_families().values() for l in ls} |
+                    {"gemm_generic", "gemm_wgrad", "gemm_wgrad_splitk", "gemm_fwd_bias", "gemm_fwd_bias_gelu"})
+    L.clipmi_prof_arm.argtypes = [ctypes.c_char_p, ctypes.c_int]
+    L.clipmi_prof_read_labels.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    _lib.check(L.clipmi_prof_arm(",".join(labels).encode(), 4), "prof_arm")
+    try:
+        _lib.check(L.clipmi_gemm(kern.stream(), ctypes.byref(d)), "clipmi_gemm")
+        torch.cuda.synchronize()
+    finally:
+        L.clipmi_prof_disarm()
+    which = (ctypes.c_int * 4)()
+    n = L.clipmi_prof_read_labels(4, which)
+    assert n == 1 and labels[which[0]] == p["label"]
+    err = (C.float() - ref).abs().max().item() / max(1.0, ref.abs().max().item())
+    assert err <= tol, err

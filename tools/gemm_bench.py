@@ -1,6 +1,6 @@
 """Per-shape GEMM throughput of libclipmi on the ViT-B/16 B=1024 training shapes (GPU).
 
-GEMM_VARIANTS=0,10 (force_small_tile values; 0 = production schedule) picks the schedules;
+GEMM_VARIANTS=0,10 (force_small_tile values, clipmi/_lib.py FORCE_*; 0 = production rule) picks the schedules;
 every variant's output is checked against variant 0's on the same inputs (max rel diff);
 GEMM_TORCH=1 adds torch.matmul (hipBLASLt, plain product) for reference."""
 import os, sys
@@ -135,7 +135,7 @@ for name, M, N, Kd, akm, bkm, odt, flags, split in SHAPES:
               flush=True)
     ref = None
     for v in VARIANTS:  # 0 = production schedule, 1 = 128 tile, >= 2: 256-kernel schedule
-        kw2 = dict(kw, bias_grad=None) if (v == 1 and bg is not None) else kw
+        kw2 = dict(kw, bias_grad=None) if (v == _lib.FORCE_128 and bg is not None) else kw
         f = lambda: K.gemm(M, N, Kd, A, lda, akm, B, ldb, bkm, C, N, small_tile=v, **kw2)
         C.zero_()
         f()

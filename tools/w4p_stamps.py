@@ -30,7 +30,7 @@ SH = {"qkv_fwd": (R, 2304, 768, True, _lib.EPI_BIAS), "out_fwd": (R, 768, 768, T
       "fc2_dgrad_ma": (R, 3072, 768, False, _lib.EPI_MUL_AUX), "fc1_dgrad": (R, 768, 3072, False, 0),
       "out_dgrad": (R, 768, 768, False, 0), "qkv_k64": (R, 2304, 64, True, _lib.EPI_BIAS),
       "qkv_noepi": (R, 2304, 768, True, 0)}
-VAR = int(os.environ.get("W4P_VAR", "28"))
+VAR = int(os.environ.get("W4P_VAR", str(_lib.FORCE_W4P)))
 # diagnostic: a shape name suffixed ":a", ":b" or ":ab" runs with lda / ldb = 0 (every row of that
 # operand aliases one 128-B line: its DMAs hit the CU's own cache), to separate the memory side of
 # the main loop from the LDS-DMA / issue side.  Results are then meaningless, times are not.

@@ -38,6 +38,27 @@ class GemmDesc(ctypes.Structure):
                 ("a_scale", c_vp), ("b_scale", c_vp), ("c_scale", c_vp)]
 
 
+# clipmi_gemm_desc.force_small_tile: kernel overrides for tests and bench tools (0: the production rule).  The one
+# decode table is gemm_force() in csrc/gemm_plan.cpp; the kernel names are clipmi_gemm_plan()'s.
+FORCE_RULE = 0
+FORCE_128 = 1        # "bf16_128": the 128x128 register-staged kernel
+FORCE_ASM8 = 4       # "asm8": 8 waves, interleaved asm DMAs (round 2's weight-gradient schedule)
+FORCE_PP8 = 9        # "pp8": the 8-wave ping-pong kernel for every shape
+FORCE_W4P = 28       # "w4p": the persistent 4-wave kernel for every shape it has
+FORCE_W4P_PF = 32    # "w4p_pf": the same with the L2 prefetch of the activation operand
+FORCE_PP8_STAGGER = 100  # + xx: "pp8" with first-round stagger xx
+FORCE_FP8_8W = 40    # MXFP8 operands: "fp8_8w" for every shape
+FORCE_FP8_RULE = 41  # MXFP8 operands: the rule ("fp8_w4p" where it covers), overriding CLIPMI_FP8_VAR
+
+
+class GemmPlanInfo(ctypes.Structure):
+    _fields_ = [("kernel", ctypes.c_char_p), ("label", ctypes.c_char_p),
+                ("tile", ctypes.c_int), ("tiles_n", ctypes.c_int), ("ntiles", ctypes.c_int),
+                ("splits", ctypes.c_int), ("k_per_split", ctypes.c_int), ("raster", ctypes.c_int),
+                ("stagger", ctypes.c_int), ("specialised", ctypes.c_int), ("bias_grad", ctypes.c_int),
+                ("reduce", ctypes.c_int)]
+
+
 class ClipmiError(RuntimeError):
     pass
 
@@ -54,6 +75,7 @@ _declare("clipmi_version", ctypes.c_int, [])
 _declare("clipmi_build_digest", ctypes.c_char_p, [])
 _declare("clipmi_last_error", ctypes.c_char_p, [])
 _declare("clipmi_gemm", ctypes.c_int, [c_vp, ctypes.POINTER(GemmDesc)])
+_declare("clipmi_gemm_plan", ctypes.c_int, [ctypes.POINTER(GemmDesc), ctypes.c_int, ctypes.POINTER(GemmPlanInfo)])
 _declare("clipmi_gemm_split3_ws", ctypes.c_int64, [ctypes.c_int] * 6)
 _declare("clipmi_gemm_x3out_ws", ctypes.c_int64, [ctypes.c_int] * 2)
 _declare("clipmi_gemm_x3out_ok", ctypes.c_int, [ctypes.c_int] * 6)
@@ -122,3 +144,13 @@ def check(status: int, what: str = ""):
 
 def call(name, *args):
     check(getattr(lib(), name)(*args), name)
+
+
+def gemm_plan(d: GemmDesc, x3out: bool = False) -> dict:
+    """What clipmi_gemm (or clipmi_gemm_x3out) would launch for descriptor d (clipmi_gemm_plan): kernel name,
+    profiler label and launch geometry.  Needs no GPU; raises as the launch would on an invalid descriptor."""
+    info = GemmPlanInfo()
+    check(lib().clipmi_gemm_plan(ctypes.byref(d), int(x3out), ctypes.byref(info)), "clipmi_gemm_plan")
+    out = {n: getattr(info, n) for n, _ in GemmPlanInfo._fields_}
+    out["kernel"], out["label"] = info.kernel.decode(), info.label.decode()
+    return out

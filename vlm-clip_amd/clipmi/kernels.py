@@ -37,11 +37,12 @@ def _on_gpu(*ts):
 
 
 def gemm(M, N, K, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, *, bias=None, residual=None, ldr=0,
-         aux=None, ldaux=0, alpha=1.0, flags=0, split_k=1, workspace=None, bias_grad=None, small_tile=False,
-         split3=False):
+         aux=None, ldaux=0, alpha=1.0, flags=0, split_k=1, workspace=None, bias_grad=None,
+         small_tile=_lib.FORCE_RULE, split3=False):
     """C[m,n] = epi(alpha * sum_k A(m,k) B(n,k)); see include/clipmi.h clipmi_gemm.  split3: fp32 operands
     and output computed as a bf16x3 split product on the bf16 MFMA kernels (CLIPMI_GEMM_SPLIT3; its
-    split images and any split-K slabs in a scratch allocated here, `workspace` is not used)."""
+    split images and any split-K slabs in a scratch allocated here, `workspace` is not used).  small_tile: a
+    kernel override for tests and tools (_lib.FORCE_*; True is FORCE_128)."""
     _on_gpu(A, B, C, bias, residual, aux, workspace)
     if A.dtype != B.dtype:
         raise ValueError("A and B must share a dtype")
@@ -193,7 +194,8 @@ def layernorm_mxfp8(x, w, b, eps=1e-5):
     return out, mean, rstd
 
 
-def gemm_fp8(M, N, K, A, B, C, ldc, *, bias=None, residual=None, ldr=0, alpha=1.0, flags=0, variant=0):
+def gemm_fp8(M, N, K, A, B, C, ldc, *, bias=None, residual=None, ldr=0, alpha=1.0, flags=0,
+             variant=_lib.FORCE_RULE):
     """C[m,n] = epi(alpha * sum_k A(m,k) B(n,k)) with A [M, K], B [N, K] MXFP8 (MX8).  C is a
     tensor (bf16 / fp32) or an MX8 [M, N] (MXFP8 output: flags bias / activation only)."""
     q8o = isinstance(C, MX8)
@@ -211,6 +213,6 @@ def gemm_fp8(M, N, K, A, B, C, ldc, *, bias=None, residual=None, ldr=0, alpha=1.
     d.ab_dtype, d.c_dtype = FP8, (FP8 if q8o else dt(C))
     d.bias_dtype = dt(bias) if bias is not None else F32
     d.split_k = 1
-    d.force_small_tile = int(variant)  # 40: the 8-wave fp8 kernel instead of the persistent 4-wave one
+    d.force_small_tile = int(variant)  # _lib.FORCE_FP8_8W / FORCE_FP8_RULE
     _lib.check(_lib.lib().clipmi_gemm(stream(), ctypes.byref(d)), "clipmi_gemm")
     return C

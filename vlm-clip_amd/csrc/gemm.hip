@@ -656,31 +656,18 @@ __global__ __launch_bounds__(NT2, 1) void gemm_fp8_kernel(GemmP p) {
 template <typename OutT, int EPI>
 void launch_fp8(const GemmP& p, hipStream_t s) {
   (void)lds_optin((const void*)gemm_fp8_kernel<OutT, EPI>, PP_S * PP_STAGE);
-  GemmP q = p;
-  q.tiles_n = (p.N + BT - 1) / BT;
-  q.ntiles = q.tiles_n * ((p.M + BT - 1) / BT);
-  hipLaunchKernelGGL((gemm_fp8_kernel<OutT, EPI>), dim3(q.ntiles), dim3(NT2), PP_S * PP_STAGE, s, q);
+  hipLaunchKernelGGL((gemm_fp8_kernel<OutT, EPI>), dim3(p.ntiles), dim3(NT2), PP_S * PP_STAGE, s, p);
 }
 
-const char* dispatch_fp8(const GemmP& p, hipStream_t s, bool f32o, bool q8o, int flags) {
-  if (const char* l = dispatch_w4_fp8(p, s, f32o, q8o, flags)) return l;  // the persistent 4-wave form
-  if (q8o) {
-    switch (flags) {
-      case E8_B | E8_Q: launch_fp8<uint8_t, E8_B | E8_Q>(p, s); return "gemm_fp8_fwd_bias_qgelu_q8";
-      default: return nullptr;
-    }
+// FP8_8W: the planned row of CLIPMI_GEMM_FP8_INSTANCES
+void launch_gemm_fp8(const GemmPlan& pl, const GemmP& p, hipStream_t s) {
+#define ROW(OUT, EPI, W4F, LABEL)             \
+  if (pl.out == OUT && pl.epi == (EPI)) {     \
+    launch_fp8<OutOf<OUT>::T, (EPI)>(p, s);   \
+    return;                                   \
   }
-  if (f32o) {
-    launch_fp8<float, -1>(p, s);
-    return "gemm_fp8";
-  }
-  switch (flags) {
-    case E8_B: launch_fp8<bf16, E8_B>(p, s); return "gemm_fp8_fwd_bias";
-    case E8_B | E8_R: launch_fp8<bf16, E8_B | E8_R>(p, s); return "gemm_fp8_fwd_bias_resid";
-    case E8_B | E8_Q: launch_fp8<bf16, E8_B | E8_Q>(p, s); return "gemm_fp8_fwd_bias_qgelu";
-    case 0: launch_fp8<bf16, 0>(p, s); return "gemm_fp8";
-    default: launch_fp8<bf16, -1>(p, s); return "gemm_fp8_generic";
-  }
+  CLIPMI_GEMM_FP8_INSTANCES(ROW)
+#undef ROW
 }
 
 // ---- MXFP8 quantisation: one thread per 32-element block of a row.  scale exponent e = the
@@ -1158,193 +1145,102 @@ void launch_hp(const GemmP& p, hipStream_t s) {
   hipLaunchKernelGGL((gemm_hp_kernel<BKM, OutT, EPI>), dim3(p.ntiles), dim3(NT2), 131072, s, p);
 }
 #endif
+static_assert(PLAN_T256 == BT && PLAN_T128 == BM && PLAN_TF32 == FT && PLAN_KSTEP_BF16 == BK && PLAN_KSTEP_F32 == FK,
+              "gemm_plan.h's tile geometry is the kernels'");
+
+// ---- launch: the plan (gemm_plan.h) names the kernel and the instance; nothing is decided here.
+// The 8-wave 256-tile kernels: ASM8 is gemm256_kernel VAR 3 (interleaved asm DMAs, round 2's weight-gradient
+// schedule: the baseline of the 4-wave wgrad bitwise tests); the measured-and-rejected schedules are compiled
+// only into an EXTRA=-DCLIPMI_GEMM_EXPERIMENTS build.
 template <bool AK, bool BKM, typename OutT, int EPI, bool BG>
-void launch256(const GemmP& p, int splits, hipStream_t s, float* bias_grad) {
-  // production: the 8-wave ping-pong kernel (var 0 / 9); var 4: gemm256_kernel VAR 3 (interleaved asm
-  // DMAs, round 2's weight-gradient schedule: the baseline of the 4-wave wgrad bitwise tests).  The
-  // measured-and-rejected schedules are compiled only into an EXTRA=-DCLIPMI_GEMM_EXPERIMENTS build.
+void launch256(GemmKernel k, const GemmP& p, int splits, hipStream_t s, float* bias_grad) {
+  switch (k) {
 #ifdef CLIPMI_GEMM_EXPERIMENTS
-  if (p.var == 10 && !BG && !p.ws && splits == 1) {
-    launch_pps<AK, BKM, OutT, EPI>(p, s);
-    return;
-  }
-  if constexpr (AK && !BG) {  // var 11: half-tile pipeline (k-major A)
-    if (p.var == 11 && !p.ws && splits == 1) {
-      launch_hp<BKM, OutT, EPI>(p, s);
+    case GemmKernel::X_PPS: launch_pps<AK, BKM, OutT, EPI>(p, s); return;
+    case GemmKernel::X_HP:
+      if constexpr (AK && !BG) launch_hp<BKM, OutT, EPI>(p, s);
       return;
-    }
-  }
-  switch (p.var) {
-    case 2: launch256v<AK, BKM, OutT, EPI, BG, 0>(p, splits, s, bias_grad); return;   // all DMAs up front
-    case 3: launch256v<AK, BKM, OutT, EPI, BG, 2>(p, splits, s, bias_grad); return;   // builtin DMAs
-    case 12: launch_ppv<AK, BKM, OutT, EPI, BG, 8>(p, splits, s, bias_grad); return;  // no epilogue (timing)
-    case 13: launch_ppv<AK, BKM, OutT, EPI, BG, 16>(p, splits, s, bias_grad); return;  // DMAs between MFMAs
-    case 14: launch_ppv<AK, BKM, OutT, EPI, BG, 20>(p, splits, s, bias_grad); return;  // + no setprio
-    case 15: launch_ppv<AK, BKM, OutT, EPI, BG, 32>(p, splits, s, bias_grad); return;  // stores through LDS
-    case 16: launch_ppv<AK, BKM, OutT, EPI, BG, 64>(p, splits, s, bias_grad); return;  // direct stores only
-    case 5: launch_ppv<AK, BKM, OutT, EPI, BG, 1>(p, splits, s, bias_grad); return;
-    case 6: launch_ppv<AK, BKM, OutT, EPI, BG, 2>(p, splits, s, bias_grad); return;
-    case 7: launch_ppv<AK, BKM, OutT, EPI, BG, 3>(p, splits, s, bias_grad); return;
-    case 8: launch_ppv<AK, BKM, OutT, EPI, BG, 4>(p, splits, s, bias_grad); return;
-    default: break;
-  }
+    case GemmKernel::X_G256_DMA_FRONT: launch256v<AK, BKM, OutT, EPI, BG, 0>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_G256_DMA_BUILTIN: launch256v<AK, BKM, OutT, EPI, BG, 2>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_NO_EPILOGUE: launch_ppv<AK, BKM, OutT, EPI, BG, 8>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_DMA_BETWEEN: launch_ppv<AK, BKM, OutT, EPI, BG, 16>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_DMA_BETWEEN_NOPRIO: launch_ppv<AK, BKM, OutT, EPI, BG, 20>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_STORE_LDS: launch_ppv<AK, BKM, OutT, EPI, BG, 32>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_STORE_DIRECT: launch_ppv<AK, BKM, OutT, EPI, BG, 64>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_V1: launch_ppv<AK, BKM, OutT, EPI, BG, 1>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_V2: launch_ppv<AK, BKM, OutT, EPI, BG, 2>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_V3: launch_ppv<AK, BKM, OutT, EPI, BG, 3>(p, splits, s, bias_grad); return;
+    case GemmKernel::X_PP_V4: launch_ppv<AK, BKM, OutT, EPI, BG, 4>(p, splits, s, bias_grad); return;
 #endif
-  if (p.var == 4) launch256v<AK, BKM, OutT, EPI, BG, 3>(p, splits, s, bias_grad);
-  else launch_ppv<AK, BKM, OutT, EPI, BG, 0>(p, splits, s, bias_grad);
+    case GemmKernel::ASM8: launch256v<AK, BKM, OutT, EPI, BG, 3>(p, splits, s, bias_grad); return;
+    default: launch_ppv<AK, BKM, OutT, EPI, BG, 0>(p, splits, s, bias_grad); return;
+  }
 }
 
-constexpr int E_B = CLIPMI_EPI_BIAS, E_R = CLIPMI_EPI_RESID, E_Q = CLIPMI_EPI_QGELU, E_G = CLIPMI_EPI_GELU;
-constexpr int E_P = CLIPMI_EPI_STORE_PRE, E_DQ = CLIPMI_EPI_DQGELU, E_DG = CLIPMI_EPI_DGELU, E_BETA = CLIPMI_EPI_BETA;
-constexpr int E_DA = CLIPMI_EPI_STORE_DACT, E_MA = CLIPMI_EPI_MUL_AUX;
-
-// the bf16x3 image-output products (clipmi_gemm_x3out, K' = 3K >= 2304) on the persistent 4-wave kernel; 0: the
-// 8-wave kernel (CLIPMI_GEMM_X3_W4=0, A/B; read per call)
-bool w4_x3() {
-  const char* e = getenv("CLIPMI_GEMM_X3_W4");
-  return !(e && e[0] == '0');
+// one row of CLIPMI_GEMM256_INSTANCES; the wgrad rows also with the fused bias gradient
+template <bool AK, bool BKM, int OUT, int EPI>
+bool launch256_row(const GemmPlan& pl, const GemmP& p, hipStream_t s, float* bg) {
+  using OutT = typename OutOf<OUT>::T;
+  if (pl.sel != sel_of(AK, BKM) || pl.out != OUT || pl.epi != EPI) return false;
+  if constexpr (!AK && !BKM) {
+    if (bg) {
+      launch256<AK, BKM, OutT, EPI, true>(pl.kernel, p, pl.splits, s, bg);
+      return true;
+    }
+  }
+  launch256<AK, BKM, OutT, EPI, false>(pl.kernel, p, pl.splits, s, bg);
+  return true;
+}
+template <bool AK, bool BKM, int OUT, int EPI>
+bool launch128_row(const GemmPlan& pl, const GemmP& p, hipStream_t s) {
+  if (pl.sel != sel_of(AK, BKM) || pl.out != OUT || pl.epi != EPI) return false;
+  launch_bf16<AK, BKM, typename OutOf<OUT>::T, EPI>(p, pl.splits, s);
+  return true;
 }
 
-const char* dispatch256(const GemmP& p, int splits, hipStream_t s, bool f32o, int sel, int flags, float* bg) {
-  if (sel == 0 && (p.ws || (f32o && flags == E_BETA))) {
-    if (p.var == 28 || p.var == 32) {  // the persistent 4-wave kernel (gemm4.hip; 32: with the L2 prefetch)
-      if (const char* l = dispatch_w4_wgrad(p, splits, s, flags, bg)) return l;
-    }
-    if (p.ws) {
-      if (bg) launch256<false, false, float, 0, true>(p, splits, s, bg);
-      else launch256<false, false, float, 0, false>(p, splits, s, bg);
-      return "gemm256_wgrad_splitk";
-    }
-    if (bg) launch256<false, false, float, E_BETA, true>(p, splits, s, bg);
-    else launch256<false, false, float, E_BETA, false>(p, splits, s, bg);
-    return "gemm256_wgrad";
-  }
-  if (bg) return nullptr;
-  // 28: the persistent 4-wave kernel for every shape; 32: the same with the L2 prefetch of the
-  // activation operand; 9: the 8-wave ping-pong kernel for every shape.  Experiments build only (CLIPMI_GEMM_EXPERIMENTS):
-  // 20: 4-wave kernel, one tile per workgroup; 22-25: its stamped timing builds (22 production
-  // schedule, 23 no main-loop DMAs, 24 no fragment reads, 25 neither)
-  // production (var 0): the persistent 4-wave kernel for long-K products (K >= 1536), where its main
-  // loop is 3-7 % faster than the ping-pong kernel's; at K = 768 / 512 the ping-pong kernel's 8 waves
-  // run the VALU-heavy epilogues twice as fast per SIMD (tools/w4_stamps.py, profiles/r03_*)
-  // (and for fc2's input gradient with the stored-derivative product, K = 768: 1182 vs 1215 us,
-  // profiles/r03_gemm_dact_shapes.log)
-  // and, with the L2 prefetch of the activation operand (gemm4.hip w4_prefetch), for the short-K input
-  // gradients (fc2's with the stored-derivative product, and out-proj's K = 768): 1.2-1.5 % and
-  // 3-4 % over the persistent kernel without it (profiles/r04_gemm_variants.log); the forward shapes
-  // and the long-K products measured equal or slower with it
-  const bool w4_pf = p.var == 0 && sel == 2 && (flags == E_MA || (flags == 0 && p.K <= 768));
-  const bool w4_default = p.var == 0 && (p.K >= 1536 || flags == E_MA);
-  if ((w4_default || w4_pf || p.var == 20 || (p.var >= 22 && p.var <= 25 && p.dbg) || p.var == 28 || p.var == 32) &&
-      !f32o && !p.ws && splits == 1 && (sel == 3 || sel == 2)) {
-    GemmP q = p;
-    const int dm = (p.var == 32 || w4_pf) ? 102 : (p.var == 28 || w4_default) ? 100 : p.var >= 22 ? 21 - p.var : 1;
-    if (const char* l = dispatch_w4(q, s, sel == 3, flags, dm)) return l;
-  }
-  // fp32 output of a bf16 product (the bf16 mode's fp32 residual stream: out-projection and fc2 with the
-  // residual fused; the patch embedding; the bf16x3 split products): the same kernels, fp32 epilogue
-  if (f32o && !p.ws && splits == 1 && sel == 3) {
-    if ((w4_default || p.var == 28) && (flags == E_B || flags == (E_B | E_R) || flags == 0 || (p.x3o && w4_x3()))) {
-      if (const char* l = dispatch_w4_f32(p, s, flags, true)) return l;
-    }
-    switch (flags) {
-      case E_B: launch256<true, true, float, E_B, false>(p, splits, s, bg); return "gemm256_fwd_bias_f32";
-      case E_B | E_R: launch256<true, true, float, E_B | E_R, false>(p, splits, s, bg); return "gemm256_fwd_bias_resid_f32";
-      case 0: launch256<true, true, float, 0, false>(p, splits, s, bg); return "gemm256_fwd_f32";
-      // the bf16x3 mode's fc1 (training: the derivative stored beside the activation; inference)
-      case E_B | E_Q | E_DA: launch256<true, true, float, E_B | E_Q | E_DA, false>(p, splits, s, bg); return "gemm256_fwd_bias_qgelu_dact_f32";
-      case E_B | E_Q: launch256<true, true, float, E_B | E_Q, false>(p, splits, s, bg); return "gemm256_fwd_bias_qgelu_f32";
-      default: break;
-    }
-  }
-  // the bf16x3 mode's input gradients (fp32 gradients; fc2's with the stored-derivative product); the plain
-  // ones (K' = 3K >= 2304) on the persistent 4-wave kernel, whose long-K main loop is the faster one
-  if (f32o && !p.ws && splits == 1 && sel == 2) {
-    if ((w4_default || p.var == 28) && (flags == 0 || (p.x3o && w4_x3()))) {
-      if (const char* l = dispatch_w4_f32(p, s, flags, false)) return l;
-    }
-    switch (flags) {
-      case 0: launch256<true, false, float, 0, false>(p, splits, s, bg); return "gemm256_dgrad_f32";
-      case E_MA: launch256<true, false, float, E_MA, false>(p, splits, s, bg); return "gemm256_dgrad_mulaux_f32";
-      default: break;
-    }
-  }
-  if (sel == 3 && !f32o) {
-    switch (flags) {
-      case E_B: launch256<true, true, bf16, E_B, false>(p, splits, s, bg); return "gemm256_fwd_bias";
-      case E_B | E_R: launch256<true, true, bf16, E_B | E_R, false>(p, splits, s, bg); return "gemm256_fwd_bias_resid";
-      case E_B | E_Q | E_P: launch256<true, true, bf16, E_B | E_Q | E_P, false>(p, splits, s, bg); return "gemm256_fwd_bias_qgelu_pre";
-      case E_B | E_Q | E_DA: launch256<true, true, bf16, E_B | E_Q | E_DA, false>(p, splits, s, bg); return "gemm256_fwd_bias_qgelu_dact";
-      case E_B | E_Q: launch256<true, true, bf16, E_B | E_Q, false>(p, splits, s, bg); return "gemm256_fwd_bias_qgelu";
-      case 0: launch256<true, true, bf16, 0, false>(p, splits, s, bg); return "gemm256_fwd";
-      default: break;
-    }
-  }
-  if (sel == 2 && !f32o) {
-    switch (flags) {
-      case 0: launch256<true, false, bf16, 0, false>(p, splits, s, bg); return "gemm256_dgrad";
-      case E_DQ: launch256<true, false, bf16, E_DQ, false>(p, splits, s, bg); return "gemm256_dgrad_dqgelu";
-      case E_MA: launch256<true, false, bf16, E_MA, false>(p, splits, s, bg); return "gemm256_dgrad_mulaux";
-      default: break;
-    }
-  }
-  return nullptr;  // not specialised: use the 128 kernel
+void launch_gemm256(const GemmPlan& pl, const GemmP& p, hipStream_t s, float* bg) {
+#define ROW(AK, BKM, OUT, EPI, SPLITK, W4F, LABEL) \
+  if (launch256_row<AK, BKM, OUT, EPI>(pl, p, s, bg)) return;
+  CLIPMI_GEMM256_INSTANCES(ROW)
+#undef ROW
 }
-
-// Specialised epilogues for the combinations the CLIP path issues; anything else takes the
-// runtime-flag instance.  Returns the variant label (also used by the live profiler).
-const char* dispatch_bf16(const GemmP& p, int splits, hipStream_t s, bool f32o, int sel, int flags) {
-  if (p.ws) {
-    if (sel == 0) { launch_bf16<false, false, float, 0>(p, splits, s); return "gemm_wgrad_splitk"; }
-    launch_bf16<true, true, float, -1>(p, splits, s);
-    return "gemm_generic";
+void launch_gemm128(const GemmPlan& pl, const GemmP& p, hipStream_t s) {
+#define ROW(AK, BKM, OUT, EPI, SPLITK, LABEL) \
+  if (launch128_row<AK, BKM, OUT, EPI>(pl, p, s)) return;
+  CLIPMI_GEMM128_INSTANCES(ROW)
+#undef ROW
+}
+// The kernel arguments of a planned product: the descriptor's operands, the plan's geometry.
+GemmP gemm_params(const clipmi_gemm_desc* d, const GemmPlan& pl, int x3o, float* colp) {
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.M = d->M; p.N = d->N; p.K = d->K;
+  p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb;
+  p.C = d->C; p.ldc = d->ldc; p.bias = d->bias; p.res = d->residual; p.ldr = d->ldr;
+  p.aux = d->aux; p.ldaux = d->ldaux; p.alpha = d->alpha; p.flags = d->flags;
+  p.bias_f32 = d->bias_dtype == CLIPMI_F32;
+  p.k_per_split = pl.k_per_split;
+  p.tiles_n = pl.tiles_n;
+  p.ntiles = pl.ntiles;
+  p.vec = pl.vec;
+  p.vec8 = pl.vec8;
+  p.raster = pl.raster;
+  p.stagger = pl.stagger;
+  if (pl.reduce) {
+    p.ws = (float*)d->workspace;
+    if (d->bias_grad) p.bws = p.ws + (int64_t)pl.splits * d->M * d->N;
   }
-  if (sel == 3 && !f32o) {
-    switch (flags) {
-      case E_B: launch_bf16<true, true, bf16, E_B>(p, splits, s); return "gemm_fwd_bias";
-      case E_B | E_R: launch_bf16<true, true, bf16, E_B | E_R>(p, splits, s); return "gemm_fwd_bias_resid";
-      case E_B | E_Q | E_P: launch_bf16<true, true, bf16, E_B | E_Q | E_P>(p, splits, s); return "gemm_fwd_bias_qgelu_pre";
-      case E_B | E_Q: launch_bf16<true, true, bf16, E_B | E_Q>(p, splits, s); return "gemm_fwd_bias_qgelu";
-      case E_B | E_G | E_P: launch_bf16<true, true, bf16, E_B | E_G | E_P>(p, splits, s); return "gemm_fwd_bias_gelu_pre";
-      case E_B | E_G: launch_bf16<true, true, bf16, E_B | E_G>(p, splits, s); return "gemm_fwd_bias_gelu";
-      case 0: launch_bf16<true, true, bf16, 0>(p, splits, s); return "gemm_fwd";
-      default: break;
-    }
-  }
-  if (sel == 2 && !f32o) {
-    switch (flags) {
-      case 0: launch_bf16<true, false, bf16, 0>(p, splits, s); return "gemm_dgrad";
-      case E_DQ: launch_bf16<true, false, bf16, E_DQ>(p, splits, s); return "gemm_dgrad_dqgelu";
-      case E_DG: launch_bf16<true, false, bf16, E_DG>(p, splits, s); return "gemm_dgrad_dgelu";
-      case E_R: launch_bf16<true, false, bf16, E_R>(p, splits, s); return "gemm_dgrad_resid";
-      default: break;
-    }
-  }
-  if (sel == 0 && f32o && flags == E_BETA) { launch_bf16<false, false, float, E_BETA>(p, splits, s); return "gemm_wgrad"; }
-  if (f32o) {
-    switch (sel) {
-      case 3: launch_bf16<true, true, float, -1>(p, splits, s); break;
-      case 2: launch_bf16<true, false, float, -1>(p, splits, s); break;
-      case 1: launch_bf16<false, true, float, -1>(p, splits, s); break;
-      default: launch_bf16<false, false, float, -1>(p, splits, s); break;
-    }
+  if (d->ab_dtype == CLIPMI_FP8) {
+    p.a_scale = (const uint8_t*)d->a_scale;
+    p.b_scale = (const uint8_t*)d->b_scale;
+    p.c_scale = d->c_scale;
   } else {
-    switch (sel) {
-      case 3: launch_bf16<true, true, bf16, -1>(p, splits, s); break;
-      case 2: launch_bf16<true, false, bf16, -1>(p, splits, s); break;
-      case 1: launch_bf16<false, true, bf16, -1>(p, splits, s); break;
-      default: launch_bf16<false, false, bf16, -1>(p, splits, s); break;
-    }
+    p.dbg = gemm_stamp_buffer();
+    p.first_round = num_cus();
   }
-  return "gemm_generic";
-}
-
-// tile-rows per raster group of the 256x256 kernels; CLIPMI_RASTER overrides (0 = row-major).
-// Defaults from profiles/r02_raster_ab.log: bf16 row-major (groups of 4/8/16: within +-3 %, no
-// consistent winner), fp8 groups of 8 (fc1 +10 %, the rest neutral).
-int raster_rows(bool fp8 = false) {
-  const char* e = getenv("CLIPMI_RASTER");  // read per call (tests switch it at run time)
-  const int r = e ? atoi(e) : -1;
-  return r >= 0 ? r : (fp8 ? 8 : 0);
+  p.x3o = x3o;
+  p.colp = colp;
+  return p;
 }
 
 }  // namespace
@@ -1390,15 +1286,13 @@ extern "C" int clipmi_gemm_batched(void* stream, const clipmi_gemm_desc* d, int 
     }
     return CLIPMI_OK;
   }
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.M = d->M; p.N = d->N; p.K = d->K;
-  p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb;
-  p.C = d->C; p.ldc = d->ldc; p.alpha = d->alpha; p.flags = d->flags;
-  p.k_per_split = d->K > 0 ? d->K : 1;
-  p.tiles_n = (d->N + FT - 1) / FT;
-  p.ntiles = p.tiles_n * ((d->M + FT - 1) / FT);
-  p.vec = (d->ldc % 4 == 0) && ((uintptr_t)d->C % 16 == 0) && (sc1 % 4 == 0) && (sc2 % 4 == 0);
+  GemmPlan pl = {};
+  pl.kernel = GemmKernel::F32_SIMT;
+  pl.splits = 1;
+  pl.k_per_split = d->K > 0 ? d->K : 1;
+  gemm_plan_tiles(&pl, d->M, d->N, FT);
+  pl.vec = (d->ldc % 4 == 0) && ((uintptr_t)d->C % 16 == 0) && (sc1 % 4 == 0) && (sc2 % 4 == 0);
+  GemmP p = gemm_params(d, pl, 0, nullptr);
   p.nb2 = nb2;
   p.bsa1 = sa1; p.bsa2 = sa2; p.bsb1 = sb1; p.bsb2 = sb2; p.bsc1 = sc1; p.bsc2 = sc2;
   const double flops = 2.0 * d->M * d->N * d->K * nb1 * nb2;
@@ -1473,7 +1367,9 @@ int split3_operand(hipStream_t s, const float* X, int64_t ldx, int rows, int K, 
   return CLIPMI_OK;
 }
 
-int gemm_split3(hipStream_t s, const clipmi_gemm_desc* d) {
+// the derived bf16 product of a CLIPMI_GEMM_SPLIT3 descriptor: validated, then (derived == nullptr) split and run, or
+// (the plan query) only described
+int gemm_split3(hipStream_t s, const clipmi_gemm_desc* d, clipmi_gemm_desc* derived = nullptr) {
   CLIPMI_REQUIRE(d->ab_dtype == CLIPMI_F32 && d->c_dtype == CLIPMI_F32, "split3: fp32 operands and output");
   CLIPMI_REQUIRE(!d->bias_grad, "split3: the fused bias gradient would sum the split image (use clipmi_colsum)");
   CLIPMI_REQUIRE((!d->a_kmajor && !d->b_kmajor) || d->K % 8 == 0, "split3: K % 8 == 0 with a k-major operand");
@@ -1481,14 +1377,16 @@ int gemm_split3(hipStream_t s, const clipmi_gemm_desc* d) {
   const int64_t need = clipmi_gemm_split3_ws(d->M, d->N, d->K, d->a_kmajor, d->b_kmajor, d->split_k);
   CLIPMI_REQUIRE(d->workspace && d->workspace_bytes >= need && ((uintptr_t)d->workspace & 255) == 0,
                  "split3: workspace too small or not 256-byte aligned (clipmi_gemm_split3_ws)");
-  if (d->M == 0 || d->N == 0) return CLIPMI_OK;
+  if (!derived && (d->M == 0 || d->N == 0)) return CLIPMI_OK;
   char* w = (char*)d->workspace;
   const int64_t a_bytes = al256b(split3_elems(d->M, d->K, d->a_kmajor) * 2);
   const int64_t b_bytes = al256b(split3_elems(d->N, d->K, d->b_kmajor) * 2);
   bf16* A3 = (bf16*)w;
   bf16* B3 = (bf16*)(w + a_bytes);
-  CLIPMI_TRY(split3_operand(s, (const float*)d->A, d->lda, d->M, d->K, d->a_kmajor, A3, 0));
-  CLIPMI_TRY(split3_operand(s, (const float*)d->B, d->ldb, d->N, d->K, d->b_kmajor, B3, 1));
+  if (!derived) {
+    CLIPMI_TRY(split3_operand(s, (const float*)d->A, d->lda, d->M, d->K, d->a_kmajor, A3, 0));
+    CLIPMI_TRY(split3_operand(s, (const float*)d->B, d->ldb, d->N, d->K, d->b_kmajor, B3, 1));
+  }
   clipmi_gemm_desc e = *d;
   e.flags &= ~CLIPMI_GEMM_SPLIT3;
   e.ab_dtype = CLIPMI_BF16;
@@ -1499,6 +1397,10 @@ int gemm_split3(hipStream_t s, const clipmi_gemm_desc* d) {
   e.ldb = d->b_kmajor ? (int64_t)3 * d->K : (d->N + 7) / 8 * 8;
   e.workspace = w + a_bytes + b_bytes;
   e.workspace_bytes = d->workspace_bytes - a_bytes - b_bytes;
+  if (derived) {
+    *derived = e;
+    return CLIPMI_OK;
+  }
   return clipmi_gemm((void*)s, &e);
 }
 }  // namespace
@@ -1520,219 +1422,101 @@ extern "C" int64_t clipmi_gemm_split3_ws(int M, int N, int K, int a_kmajor, int 
 }
 
 namespace {
-// clipmi_gemm with the bf16x3 image output of clipmi_gemm_x3out (x3o 1 / 2: pattern 0 / 1, colp: column partials)
-int gemm_impl(void* stream, const clipmi_gemm_desc* d, int x3o, float* colp) {
-  hipStream_t s = (hipStream_t)stream;
-  CLIPMI_REQUIRE(d && d->M >= 0 && d->N >= 0 && d->K >= 0, "bad shape");
-  // every operand an epilogue flag reads or writes must be given (a null one would fault the GPU)
-  {
-    constexpr int AUXF = CLIPMI_EPI_DQGELU | CLIPMI_EPI_DGELU | CLIPMI_EPI_STORE_PRE | CLIPMI_EPI_STORE_DACT |
-                         CLIPMI_EPI_MUL_AUX;
-    CLIPMI_REQUIRE(!(d->flags & AUXF) || (d->aux && d->ldaux >= d->N), "epilogue flags need aux (ldaux >= N)");
-    CLIPMI_REQUIRE(!(d->flags & CLIPMI_EPI_RESID) || (d->residual && d->ldr >= d->N), "residual flag needs residual (ldr >= N)");
-    CLIPMI_REQUIRE(!(d->flags & CLIPMI_EPI_BIAS) || d->bias, "bias flag needs bias");
-    CLIPMI_REQUIRE(!(d->flags & CLIPMI_EPI_STORE_DACT) || (d->flags & (CLIPMI_EPI_QGELU | CLIPMI_EPI_GELU)),
-                   "store_dact needs an activation flag");
-    CLIPMI_REQUIRE((d->flags & ~(1023 | CLIPMI_GEMM_SPLIT3)) == 0, "unknown epilogue flag");
-    // aux has one role per launch, and the epilogues read one input stream besides it
-    constexpr int AUXR = CLIPMI_EPI_DQGELU | CLIPMI_EPI_DGELU | CLIPMI_EPI_MUL_AUX;
-    constexpr int AUXW = CLIPMI_EPI_STORE_PRE | CLIPMI_EPI_STORE_DACT;
-    CLIPMI_REQUIRE((d->flags & AUXW) != AUXW, "store_pre and store_dact both write aux");
-    CLIPMI_REQUIRE(!((d->flags & AUXR) && (d->flags & AUXW)), "aux cannot be both read and written");
-    CLIPMI_REQUIRE(__builtin_popcount(d->flags & AUXR) <= 1, "at most one aux-reading flag");
-    CLIPMI_REQUIRE(!((d->flags & CLIPMI_EPI_MUL_AUX) && (d->flags & (CLIPMI_EPI_RESID | CLIPMI_EPI_BETA))),
-                   "mul_aux cannot be combined with residual / beta");
-  }
-  if (d->flags & CLIPMI_GEMM_SPLIT3) return gemm_split3(s, d);
-  if (d->ab_dtype == CLIPMI_FP8) {  // MXFP8 operands (see include/clipmi.h)
-    CLIPMI_REQUIRE(d->a_kmajor && d->b_kmajor, "fp8: both operands k-major");
-    CLIPMI_REQUIRE(d->K % 128 == 0 && d->lda % 16 == 0 && d->ldb % 16 == 0, "fp8: K % 128 == 0, lda/ldb % 16 == 0");
-    CLIPMI_REQUIRE(d->a_scale && d->b_scale, "fp8: block scales required");
-    CLIPMI_REQUIRE(((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->B & 15) == 0, "fp8: A/B 16-byte aligned");
-    CLIPMI_REQUIRE(d->c_dtype == CLIPMI_F32 || d->c_dtype == CLIPMI_BF16 || d->c_dtype == CLIPMI_FP8, "c_dtype");
-    CLIPMI_REQUIRE(d->split_k <= 1 && !d->bias_grad, "fp8: forward GEMMs only");
-    const bool q8o = d->c_dtype == CLIPMI_FP8;
-    // epilogue_q8 writes each row's e4m3 bytes as 16-B stores and a row's two scale bytes as one 16-bit store
-    CLIPMI_REQUIRE(!q8o || (d->c_scale && d->ldc == d->N && d->N % 32 == 0 && ((uintptr_t)d->C & 15) == 0 &&
-                            ((uintptr_t)d->c_scale & 1) == 0),
-                   "fp8 output: c_scale (2-byte aligned), ldc == N, N % 32 == 0, C 16-byte aligned");
-    if (d->M == 0 || d->N == 0) return CLIPMI_OK;
-    GemmP p;
-    memset(&p, 0, sizeof(p));
-    p.M = d->M; p.N = d->N; p.K = d->K;
-    p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb;
-    p.C = d->C; p.ldc = d->ldc; p.bias = d->bias; p.res = d->residual; p.ldr = d->ldr;
-    p.aux = d->aux; p.ldaux = d->ldaux; p.alpha = d->alpha; p.flags = d->flags;
-    p.bias_f32 = d->bias_dtype == CLIPMI_F32;
-    p.k_per_split = d->K;
-    p.a_scale = (const uint8_t*)d->a_scale;
-    p.b_scale = (const uint8_t*)d->b_scale;
-    p.c_scale = d->c_scale;
-    p.raster = raster_rows(true);
-    p.var = d->force_small_tile;  // 40: the 8-wave fp8 kernel (A/B of the persistent 4-wave one)
-    {
-      static const int env = [] {  // CLIPMI_FP8_VAR=40 / 41: every fp8 product on the 8-wave / 4-wave kernel (A/B)
-        const char* e = getenv("CLIPMI_FP8_VAR");
-        return e ? atoi(e) : 0;
-      }();
-      if (p.var == 0 && (env == 40 || env == 41)) p.var = env;
-    }
-    p.vec = (d->ldc % 4 == 0) && (d->ldr % 4 == 0) && (d->ldaux % 4 == 0) && ((uintptr_t)d->C % 16 == 0) &&
-            ((uintptr_t)d->residual % 16 == 0) && ((uintptr_t)d->aux % 16 == 0);
-    p.vec8 = d->c_dtype == CLIPMI_BF16 && d->N % 8 == 0 && d->ldc % 8 == 0 && d->ldr % 8 == 0 && d->ldaux % 8 == 0 &&
-             ((uintptr_t)d->C % 16 == 0) && ((uintptr_t)d->residual % 16 == 0) && ((uintptr_t)d->aux % 16 == 0) &&
-             ((uintptr_t)d->bias % 16 == 0);
-    const double flops = 2.0 * d->M * d->N * d->K;
-    ProfScope ps(s, nullptr, 0.0);
-    const char* label = dispatch_fp8(p, s, d->c_dtype == CLIPMI_F32, q8o, d->flags);
-    if (!label) return clipmi_invalid("fp8 output: supported epilogue flags are bias + quick_gelu");
-    ps.finish(label, flops);
-    CLIPMI_CHECK_LAUNCH();
-    return CLIPMI_OK;
-  }
-  const bool bf = d->ab_dtype == CLIPMI_BF16;
-  CLIPMI_REQUIRE(bf || d->ab_dtype == CLIPMI_F32, "ab_dtype");
-  if (d->M == 0 || d->N == 0) return CLIPMI_OK;
-  CLIPMI_REQUIRE(bf == false || d->b_kmajor || d->N % 8 == 0, "row-major B needs N % 8 == 0");
-  CLIPMI_REQUIRE(d->c_dtype == CLIPMI_F32 || d->c_dtype == CLIPMI_BF16, "c_dtype");
-
-  if (bf) {
-    CLIPMI_REQUIRE(!d->a_kmajor || d->K % 8 == 0, "k-major A needs K % 8 == 0");
-    CLIPMI_REQUIRE(!d->b_kmajor || d->K % 8 == 0, "k-major B needs K % 8 == 0");
-    CLIPMI_REQUIRE(d->a_kmajor || d->M % 8 == 0, "row-major A needs M % 8 == 0");
-    CLIPMI_REQUIRE(d->a_kmajor || d->M >= 8, "M >= 8");
-    CLIPMI_REQUIRE(((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->B & 15) == 0, "A/B must be 16-byte aligned");
-    CLIPMI_REQUIRE((d->lda % 8) == 0 && (d->ldb % 8) == 0, "lda/ldb must be multiples of 8");
-  }
-  int splits = d->split_k > 1 ? d->split_k : 1;
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.M = d->M; p.N = d->N; p.K = d->K;
-  p.A = d->A; p.lda = d->lda; p.B = d->B; p.ldb = d->ldb;
-  p.C = d->C; p.ldc = d->ldc; p.bias = d->bias; p.res = d->residual; p.ldr = d->ldr;
-  p.aux = d->aux; p.ldaux = d->ldaux; p.alpha = d->alpha; p.flags = d->flags;
-  p.bias_f32 = d->bias_dtype == CLIPMI_F32;
-  p.ws = nullptr;
-  p.bws = nullptr;
-  p.x3o = x3o;
-  p.colp = colp;
-  // 256-kernel schedule: the ping-pong kernel for the forward / dgrad layouts, the
-  // single-group asm-DMA schedule (var 4) for wgrad, where its 64-k steps measured faster
-  // (profiles/r01_gemm_variants*.log).  CLIPMI_GEMM_VAR overrides it for A/B runs.
-  // (CLIPMI_GEMM_VAR: forward/dgrad layouts, CLIPMI_GEMM_WVAR: wgrad layout)
-  static const int env_var = [] {
-    const char* e = getenv("CLIPMI_GEMM_VAR");
-    return e ? atoi(e) : -1;
-  }();
-  static const int env_wvar = [] {
-    const char* e = getenv("CLIPMI_GEMM_WVAR");
-    return e ? atoi(e) : -1;
-  }();
-  const bool wlayout = !d->a_kmajor && !d->b_kmajor;
-  const int evar = wlayout ? env_wvar : env_var;
-  p.raster = raster_rows();
-  p.dbg = gemm_stamp_buffer();
-  p.stagger = 0;
-  p.first_round = num_cus();
-  if (d->force_small_tile >= 100 && d->force_small_tile < 200) {  // 1xx the 8-wave kernel, first-round stagger xx
-    p.var = 9;
-    p.stagger = d->force_small_tile % 100;
-  } else if (d->force_small_tile >= 2) p.var = d->force_small_tile;
-  else if (evar >= 0 && d->force_small_tile == 0) p.var = evar;
-  else p.var = wlayout ? 28 : 0;  // wgrad: the persistent 4-wave kernel (5-11 % over var 4, profiles/r03_wgrad_4wave.log)
-  p.vec = (d->ldc % 4 == 0) && (d->ldr % 4 == 0) && (d->ldaux % 4 == 0) && ((uintptr_t)d->C % 16 == 0) &&
-          ((uintptr_t)d->residual % 16 == 0) && ((uintptr_t)d->aux % 16 == 0);
-  p.vec8 = d->c_dtype == CLIPMI_BF16 && d->N % 8 == 0 && d->ldc % 8 == 0 && d->ldr % 8 == 0 && d->ldaux % 8 == 0 &&
-           ((uintptr_t)d->C % 16 == 0) && ((uintptr_t)d->residual % 16 == 0) && ((uintptr_t)d->aux % 16 == 0) &&
-           ((uintptr_t)d->bias % 16 == 0);
-  // 256x256 LDS-DMA kernel for the big shapes (k-major operands need K % 64 == 0: the
-  // buffer range check zero-fills rows, not a row's k tail)
-  const bool kok = (!d->a_kmajor || d->K % 64 == 0) && (!d->b_kmajor || d->K % 64 == 0);
-  const bool use256 = bf && kok && ((d->M >= 256 && d->N >= 128) || d->bias_grad) && d->force_small_tile != 1;
-  CLIPMI_REQUIRE(!d->bias_grad || use256, "bias_grad fusion needs the 256 kernel (bf16, wgrad layout)");
-  CLIPMI_REQUIRE(!x3o || (use256 && splits == 1), "x3out: needs the 256-tile kernels (M >= 256, N >= 128, K % 64 == 0)");
-  const int tile = bf ? (use256 ? BT : BM) : FT;
-  const int kstep = bf ? BK : FK;
-  if (splits > 1) {
-    CLIPMI_REQUIRE(d->c_dtype == CLIPMI_F32, "split_k needs fp32 C");
-    CLIPMI_REQUIRE((d->flags & ~CLIPMI_EPI_BETA) == 0, "split_k supports only the beta flag");
-    CLIPMI_REQUIRE(d->workspace && d->workspace_bytes >= (int64_t)splits * d->M * (d->N + (d->bias_grad ? 1 : 0)) * 4,
-                   "split_k workspace too small (split_k * M * (N + bias_grad ? 1 : 0) floats)");
-    int per = (d->K + splits - 1) / splits;
-    per = (per + kstep - 1) / kstep * kstep;
-    splits = (d->K + per - 1) / per;
-    p.k_per_split = per;
-    p.ws = (float*)d->workspace;
-    if (d->bias_grad) p.bws = p.ws + (int64_t)splits * d->M * d->N;
+// the second stage of a split-K product: slabs -> C (and bias partials -> bias_grad)
+int splitk_reduce(hipStream_t s, const clipmi_gemm_desc* d, const GemmPlan& pl, const GemmP& p) {
+  const int64_t total = (int64_t)d->M * d->N;
+  const int beta = (d->flags & CLIPMI_EPI_BETA) ? 1 : 0;
+  if (pl.reduce == 1) {
+    DeferredReduce r;
+    memset(&r, 0, sizeof(r));
+    r.kind = 1;
+    r.ws = p.ws; r.C = (float*)d->C; r.ldc = d->ldc; r.M = d->M; r.N = d->N; r.splits = pl.splits;
+    r.alpha = d->alpha; r.beta = beta; r.bws = p.bws; r.bias_grad = d->bias_grad;
+    DeferredReduce* slot = deferred_slot();
+    if (slot && slot->kind == 0) *slot = r;  // executed by the next persistent GEMM launch
+    else CLIPMI_TRY(launch_deferred(s, r));
   } else {
-    p.k_per_split = d->K > 0 ? d->K : 1;
-  }
-  p.tiles_n = (d->N + tile - 1) / tile;
-  p.ntiles = p.tiles_n * ((d->M + tile - 1) / tile);
-  const double flops = 2.0 * d->M * d->N * d->K;
-  if (bf) {
-    const bool f32o = d->c_dtype == CLIPMI_F32 || p.ws;
-    const int sel = (d->a_kmajor ? 2 : 0) | (d->b_kmajor ? 1 : 0);
-    // the label is only known after dispatch; probe the profiler with the would-be label first
-    ProfScope ps(s, nullptr, 0.0);
-    const char* label = nullptr;
-    if (use256) {
-      GemmP q = p;
-      q.tiles_n = (d->N + BT - 1) / BT;
-      q.ntiles = q.tiles_n * ((d->M + BT - 1) / BT);
-      // weight gradients with more column than row tiles (fc2: M = 768, N = 3072) walk each k-slab's
-      // tiles column-major, so the ~32 items an XCD holds at once share the few row panels instead of
-      // spanning every column panel (L2 fetch modelled 1.66x -> 1.25x of the compulsory panels,
-      // tools/gemm_l2_model.py); CLIPMI_RASTER overrides
-      if (wlayout && !getenv("CLIPMI_RASTER") && q.tiles_n > q.ntiles / q.tiles_n) q.raster = q.ntiles / q.tiles_n;
-      label = dispatch256(q, splits, s, f32o, sel, d->flags, d->bias_grad);
-      CLIPMI_REQUIRE(label || !x3o, "x3out: no image-output kernel for these flags");
-    }
-    if (!label) {
-      CLIPMI_REQUIRE(!d->bias_grad, "bias_grad needs the wgrad layout (both operands row-major in k)");
-      GemmP q = p;  // 128-tile grid (p's tile counts may be sized for the 256 kernel)
-      q.tiles_n = (d->N + BM - 1) / BM;
-      q.ntiles = q.tiles_n * ((d->M + BM - 1) / BM);
-      label = dispatch_bf16(q, splits, s, f32o, sel, d->flags);
-    }
-    CLIPMI_REQUIRE(label, "no kernel for this GEMM");
-    ps.finish(label, flops);
-  } else {
-    ProfScope ps(s, nullptr, 0.0);
-    if (d->c_dtype == CLIPMI_F32 || p.ws)
-      hipLaunchKernelGGL(gemm_f32_kernel<float>, dim3(p.ntiles, splits), dim3(256), 0, s, p, d->a_kmajor, d->b_kmajor);
-    else
-      hipLaunchKernelGGL(gemm_f32_kernel<bf16>, dim3(p.ntiles, splits), dim3(256), 0, s, p, d->a_kmajor, d->b_kmajor);
-    ps.finish("gemm_f32", flops);
+    const unsigned nblk = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nblk), dim3(256), 0, s,
+                       p.ws, (float*)d->C, d->ldc, d->M, d->N, pl.splits, d->alpha, beta);
+    if (p.bws)
+      hipLaunchKernelGGL(bias_partials_reduce_kernel, dim3((d->M + 255) / 256), dim3(256), 0, s, p.bws,
+                         d->bias_grad, d->M, pl.splits);
   }
   CLIPMI_CHECK_LAUNCH();
-  if (p.ws) {
-    const int64_t total = (int64_t)d->M * d->N;
-    const int beta = (d->flags & CLIPMI_EPI_BETA) ? 1 : 0;
-    if (d->N % 4 == 0 && d->ldc % 4 == 0 && ((uintptr_t)d->C & 15) == 0 && ((uintptr_t)p.ws & 15) == 0) {
-      DeferredReduce r;
-      memset(&r, 0, sizeof(r));
-      r.kind = 1;
-      r.ws = p.ws; r.C = (float*)d->C; r.ldc = d->ldc; r.M = d->M; r.N = d->N; r.splits = splits;
-      r.alpha = d->alpha; r.beta = beta; r.bws = p.bws; r.bias_grad = d->bias_grad;
-      DeferredReduce* slot = deferred_slot();
-      if (slot && slot->kind == 0) *slot = r;  // executed by the next persistent GEMM launch
-      else CLIPMI_TRY(launch_deferred(s, r));
-    } else {
-      const unsigned nblk = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nblk), dim3(256), 0, s,
-                         p.ws, (float*)d->C, d->ldc, d->M, d->N, splits, d->alpha, beta);
-      if (p.bws)
-        hipLaunchKernelGGL(bias_partials_reduce_kernel, dim3((d->M + 255) / 256), dim3(256), 0, s, p.bws,
-                           d->bias_grad, d->M, splits);
-    }
-    CLIPMI_CHECK_LAUNCH();
+  return CLIPMI_OK;
+}
+
+void launch_gemm_f32(const GemmPlan& pl, const GemmP& p, hipStream_t s) {
+  const bool ak = pl.sel & 2, bkm = pl.sel & 1;
+  if (pl.out == CLIPMI_F32)
+    hipLaunchKernelGGL(gemm_f32_kernel<float>, dim3(p.ntiles, pl.splits), dim3(256), 0, s, p, ak, bkm);
+  else
+    hipLaunchKernelGGL(gemm_f32_kernel<bf16>, dim3(p.ntiles, pl.splits), dim3(256), 0, s, p, ak, bkm);
+}
+
+void launch_gemm(const GemmPlan& pl, const GemmP& p, hipStream_t s, float* bg) {
+  switch (pl.kernel) {
+    case GemmKernel::F32_SIMT: launch_gemm_f32(pl, p, s); return;
+    case GemmKernel::BF16_128: launch_gemm128(pl, p, s); return;
+    case GemmKernel::FP8_8W: launch_gemm_fp8(pl, p, s); return;
+    case GemmKernel::FP8_W4P: launch_gemm_fp8_w4(pl, p, s); return;
+    case GemmKernel::W4P:
+    case GemmKernel::W4P_PF:
+#ifdef CLIPMI_GEMM_EXPERIMENTS
+    case GemmKernel::X_W4_ONE:
+    case GemmKernel::X_W4_STAMP0:
+    case GemmKernel::X_W4_STAMP1:
+    case GemmKernel::X_W4_STAMP2:
+    case GemmKernel::X_W4_STAMP3:
+#endif
+      launch_gemm_w4(pl, p, s, bg);
+      return;
+    default: launch_gemm256(pl, p, s, bg); return;  // the 8-wave 256-tile kernels
   }
+}
+
+// clipmi_gemm, and with x3o clipmi_gemm_x3out's image output (x3o 1 / 2: pattern 0 / 1, colp: column partials):
+// plan, launch the planned kernel, then the split-K reduce when the plan has one
+int gemm_impl(void* stream, const clipmi_gemm_desc* d, int x3o, float* colp) {
+  hipStream_t s = (hipStream_t)stream;
+  GemmPlan pl;
+  CLIPMI_TRY(gemm_plan(d, x3o, gemm_env(), &pl));
+  if (pl.split3) return gemm_split3(s, d);
+  if (pl.kernel == GemmKernel::NONE) return CLIPMI_OK;
+  const GemmP p = gemm_params(d, pl, x3o, colp);
+  ProfScope ps(s, nullptr, 0.0);
+  launch_gemm(pl, p, s, d->bias_grad);
+  ps.finish(pl.label, 2.0 * d->M * d->N * d->K);
+  CLIPMI_CHECK_LAUNCH();
+  if (pl.reduce) CLIPMI_TRY(splitk_reduce(s, d, pl, p));
   return CLIPMI_OK;
 }
 }  // namespace
 
 extern "C" int clipmi_gemm(void* stream, const clipmi_gemm_desc* d) { return gemm_impl(stream, d, 0, nullptr); }
+
+// What clipmi_gemm (x3out 0) or clipmi_gemm_x3out (x3out 1) would launch for d, from the same gemm_plan();
+// nothing is launched and no operand is read.
+extern "C" int clipmi_gemm_plan(const clipmi_gemm_desc* d, int x3out, clipmi_gemm_plan_info* out) {
+  CLIPMI_REQUIRE(out, "out");
+  GemmPlan pl;
+  CLIPMI_TRY(gemm_plan(d, x3out ? 1 : 0, gemm_env(), &pl));
+  if (pl.split3) {
+    clipmi_gemm_desc e;
+    CLIPMI_TRY(gemm_split3(nullptr, d, &e));
+    CLIPMI_TRY(gemm_plan(&e, 0, gemm_env(), &pl));
+  }
+  out->kernel = gemm_kernel_name(pl.kernel);
+  out->label = pl.label;
+  out->tile = pl.tile; out->tiles_n = pl.tiles_n; out->ntiles = pl.ntiles;
+  out->splits = pl.splits; out->k_per_split = pl.k_per_split;
+  out->raster = pl.raster; out->stagger = pl.stagger;
+  out->specialised = pl.specialised;
+  out->bias_grad = pl.bias_grad;
+  out->reduce = pl.reduce;
+  return CLIPMI_OK;
+}
 
 namespace {
 __global__ __launch_bounds__(256) void fold_rows4_kernel(const float* part, int P, int N, int per, float* out) {

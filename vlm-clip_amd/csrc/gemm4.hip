@@ -685,38 +685,27 @@ void launch_w4p(const GemmP& p, int splits, hipStream_t s, float* bias_grad) {
   hipLaunchKernelGGL((gemm_w4p_kernel<AK, BKM, OutT, EPI, BG, PF>), dim3(grid), dim3(W4_THR), L, s, q, bias_grad);
 }
 
-// dm: 100 persistent, 102 persistent with the L2 prefetch; experiments build only:
-// 1 one tile per workgroup, < 0 the stamped diagnostic builds.  Returns false when not built.
-template <bool BKM, int EPI>
-bool launch_w4(const GemmP& p, hipStream_t s, int dm) {
-  if (dm == 100) {
-    launch_w4p<true, BKM, bf16, EPI, false>(p, 1, s, nullptr);
-    return true;
-  }
-  if (dm == 102) {  // L2 prefetch of the activation operand
-    launch_w4p<true, BKM, bf16, EPI, false, true>(p, 1, s, nullptr);
-    return true;
-  }
 #ifdef CLIPMI_GEMM_EXPERIMENTS
-  if (dm < 0) {  // diagnostic stamp builds
-    constexpr int L = 2 * W4_STAGE + 4 * W4_NST * 8;
+// one tile per workgroup (X_W4_ONE) and its stamped timing builds (X_W4_STAMP0-3)
+template <bool BKM, int EPI>
+void launch_w4_one(GemmKernel k, const GemmP& p, hipStream_t s) {
+  if (k == GemmKernel::X_W4_ONE) {
+    (void)lds_optin((const void*)gemm_w4_kernel<BKM, bf16, EPI>, 2 * W4_STAGE);
+    hipLaunchKernelGGL((gemm_w4_kernel<BKM, bf16, EPI>), dim3(p.ntiles), dim3(W4_THR), 2 * W4_STAGE, s, p);
+    return;
+  }
+  constexpr int L = 2 * W4_STAGE + 4 * W4_NST * 8;
 #define W4_ST(n)                                                                                              \
   (void)lds_optin((const void*)gemm_w4_kernel<BKM, bf16, EPI, true, n>, L);                                  \
   hipLaunchKernelGGL((gemm_w4_kernel<BKM, bf16, EPI, true, n>), dim3(p.ntiles), dim3(W4_THR), L, s, p)
-    if (dm == -1) { W4_ST(0); }
-    else if (dm == -2) { W4_ST(1); }
-    else if (dm == -3) { W4_ST(2); }
-    else { W4_ST(3); }
+  if (k == GemmKernel::X_W4_STAMP0) { W4_ST(0); }
+  else if (k == GemmKernel::X_W4_STAMP1) { W4_ST(1); }
+  else if (k == GemmKernel::X_W4_STAMP2) { W4_ST(2); }
+  else { W4_ST(3); }
 #undef W4_ST
-    return true;
-  }
-  (void)lds_optin((const void*)gemm_w4_kernel<BKM, bf16, EPI>, 2 * W4_STAGE);
-  hipLaunchKernelGGL((gemm_w4_kernel<BKM, bf16, EPI>), dim3(p.ntiles), dim3(W4_THR), 2 * W4_STAGE, s, p);
-  return true;
-#else
-  return false;
-#endif
 }
+#endif
+
 
 
 // ------------------------------------------------------------------ MXFP8 (config 5)
@@ -982,120 +971,63 @@ template <typename OutT, int EPI>
 void launch_w4p8(const GemmP& p, hipStream_t s) {
   constexpr int L = 2 * W4_STAGE + 4 * 8192;
   (void)lds_optin((const void*)gemm_w4p8_kernel<OutT, EPI>, L);
-  GemmP q = p;
-  q.tiles_n = (p.N + BT - 1) / BT;
-  q.ntiles = q.tiles_n * ((p.M + BT - 1) / BT);
-  const int grid = std::min(q.ntiles, num_cus_w4());
-  hipLaunchKernelGGL((gemm_w4p8_kernel<OutT, EPI>), dim3(grid), dim3(W4_THR), L, s, q);
+  const int grid = std::min(p.ntiles, num_cus_w4());
+  hipLaunchKernelGGL((gemm_w4p8_kernel<OutT, EPI>), dim3(grid), dim3(W4_THR), L, s, p);
 }
 }  // namespace
 
-// forward (k-major B) and dgrad (row-major-in-k B) products with bf16 output and one of the
-// CLIP path's epilogues; returns the profiler label, or nullptr when not covered.
-// dm: 1 one tile per workgroup, 100 persistent, < 0 the stamped diagnostic builds.
-const char* dispatch_w4(const GemmP& p, hipStream_t s, bool bkm, int flags, int dm) {
-  constexpr int E_B = CLIPMI_EPI_BIAS, E_R = CLIPMI_EPI_RESID, E_Q = CLIPMI_EPI_QGELU;
-  constexpr int E_P = CLIPMI_EPI_STORE_PRE, E_DQ = CLIPMI_EPI_DQGELU;
-  constexpr int E_DA = CLIPMI_EPI_STORE_DACT, E_MA = CLIPMI_EPI_MUL_AUX;
-  if (bkm) {
-    switch (flags) {
-      case E_B: return launch_w4<true, E_B>(p, s, dm) ? "gemm256_fwd_bias" : nullptr;
-      case E_B | E_R: return launch_w4<true, E_B | E_R>(p, s, dm) ? "gemm256_fwd_bias_resid" : nullptr;
-      case E_B | E_Q | E_P: return launch_w4<true, E_B | E_Q | E_P>(p, s, dm) ? "gemm256_fwd_bias_qgelu_pre" : nullptr;
-      case E_B | E_Q | E_DA: return launch_w4<true, E_B | E_Q | E_DA>(p, s, dm) ? "gemm256_fwd_bias_qgelu_dact" : nullptr;
-      case E_B | E_Q: return launch_w4<true, E_B | E_Q>(p, s, dm) ? "gemm256_fwd_bias_qgelu" : nullptr;
-      case 0: return launch_w4<true, 0>(p, s, dm) ? "gemm256_fwd" : nullptr;
-      default: return nullptr;
-    }
-  }
-  switch (flags) {
-    case 0: return launch_w4<false, 0>(p, s, dm) ? "gemm256_dgrad" : nullptr;
-    case E_DQ: return launch_w4<false, E_DQ>(p, s, dm) ? "gemm256_dgrad_dqgelu" : nullptr;
-    case E_MA: return launch_w4<false, E_MA>(p, s, dm) ? "gemm256_dgrad_mulaux" : nullptr;
-    default: return nullptr;
-  }
-}
-
-// fp32-output forward products (k-major B) on the persistent kernel: the bf16 mode's fp32 residual stream
-// (fc2 with bias + residual) and fp32-output bf16 products
-const char* dispatch_w4_f32(const GemmP& p, hipStream_t s, int flags, bool bkm) {
-  constexpr int E_B = CLIPMI_EPI_BIAS, E_R = CLIPMI_EPI_RESID, E_Q = CLIPMI_EPI_QGELU;
-  constexpr int E_DA = CLIPMI_EPI_STORE_DACT, E_MA = CLIPMI_EPI_MUL_AUX;
-  if (!bkm) {  // the bf16x3 mode's input gradients (K' = 3K >= 2304), fp32 out or (fc2's, x3o) the image
-    if (flags == E_MA && p.x3o) {
-      launch_w4p<true, false, float, E_MA, false>(p, 1, s, nullptr);
-      return "gemm256_dgrad_mulaux_f32";
-    }
-    if (flags != 0) return nullptr;
-    launch_w4p<true, false, float, 0, false>(p, 1, s, nullptr);
-    return "gemm256_dgrad_f32";
-  }
-  if (p.x3o) {  // the bf16x3 mode's fc1 writing its activation's image (clipmi_gemm_x3out)
-    if (flags == (E_B | E_Q | E_DA)) {
-      launch_w4p<true, true, float, E_B | E_Q | E_DA, false>(p, 1, s, nullptr);
-      return "gemm256_fwd_bias_qgelu_dact_f32";
-    }
-    if (flags == (E_B | E_Q)) {
-      launch_w4p<true, true, float, E_B | E_Q, false>(p, 1, s, nullptr);
-      return "gemm256_fwd_bias_qgelu_f32";
-    }
-    return nullptr;
-  }
-  switch (flags) {
-    case E_B | E_R: launch_w4p<true, true, float, E_B | E_R, false>(p, 1, s, nullptr); return "gemm256_fwd_bias_resid_f32";
-    case E_B: launch_w4p<true, true, float, E_B, false>(p, 1, s, nullptr); return "gemm256_fwd_bias_f32";
-    case 0: launch_w4p<true, true, float, 0, false>(p, 1, s, nullptr); return "gemm256_fwd_f32";
-    default: return nullptr;
-  }
-}
-
-// weight gradients (both operands row-major in k, fp32 output): split-K slabs (p.ws) or the
-// beta epilogue (one split), with the fused bias gradient when bg != nullptr
-// MXFP8 forward products on the persistent 4-wave kernel: K % 256 == 0 (whole scale pairs) and at
-// least one full tile; nullptr leaves them to gemm.hip's 8-wave fp8 kernel
-// Production: every covered shape (round 5).  Round 4 kept the residual / activation epilogues at K = 1024
-// (fc1 -> MXFP8, out-proj) on the 8-wave kernel, equal or 5 % slower here in isolation
-// (profiles/r04_fp8_gemm.log); in config 5's step this kernel for all of them measured equal throughput
-// and a 3.5 % shorter mean fp8 launch (profiles/r05_cfg5_fp8_kernel_ab.log).  40: the 8-wave kernel (A/B).
-const char* dispatch_w4_fp8(const GemmP& p, hipStream_t s, bool f32o, bool q8o, int flags) {
-  if (p.K % W8_PAIR != 0 || p.M < BT || p.N < BT || p.var == 40) return nullptr;  // 40: the 8-wave kernel (A/B)
-  constexpr int B8 = CLIPMI_EPI_BIAS, Q8 = CLIPMI_EPI_QGELU, R8 = CLIPMI_EPI_RESID;
-  if (q8o) {
-    if (flags != (B8 | Q8)) return nullptr;
-    launch_w4p8<uint8_t, B8 | Q8>(p, s);
-    return "gemm_fp8_fwd_bias_qgelu_q8";
-  }
-  if (f32o) {
-    launch_w4p8<float, -1>(p, s);
-    return "gemm_fp8";
-  }
-  if (!p.vec8) return nullptr;  // the 16-B-store epilogue needs aligned bf16 rows
-  switch (flags) {
-    case B8: launch_w4p8<bf16, B8>(p, s); return "gemm_fp8_fwd_bias";
-    case B8 | R8: launch_w4p8<bf16, B8 | R8>(p, s); return "gemm_fp8_fwd_bias_resid";
-    case B8 | Q8: launch_w4p8<bf16, B8 | Q8>(p, s); return "gemm_fp8_fwd_bias_qgelu";
-    case 0: launch_w4p8<bf16, 0>(p, s); return "gemm_fp8";
-    default: return nullptr;
-  }
-}
-
-const char* dispatch_w4_wgrad(const GemmP& p, int splits, hipStream_t s, int flags, float* bg) {
-  if (p.ws) {
+// ---- launch: one row of an instance list (gemm_plan.h) -> its 4-wave kernel, when the plan names that row
+namespace {
+template <bool AK, bool BKM, int OUT, int EPI, bool SPLITK, int W4F>
+bool launch_w4_row(const GemmPlan& pl, const GemmP& p, hipStream_t s, float* bg) {
+  using OutT = typename OutOf<OUT>::T;
+  if (pl.sel != sel_of(AK, BKM) || pl.out != OUT || pl.epi != EPI) return false;
+  constexpr GemmKernel PF = GemmKernel::W4P_PF;
+  if constexpr (W4F == W4PF) {  // bf16 output, forward / dgrad
+    if (pl.kernel == GemmKernel::W4P) launch_w4p<AK, BKM, OutT, EPI, false>(p, pl.splits, s, nullptr);
+    else if (pl.kernel == PF) launch_w4p<AK, BKM, OutT, EPI, false, true>(p, pl.splits, s, nullptr);
 #ifdef CLIPMI_GEMM_EXPERIMENTS
-    if (p.var == 32) {  // L2 prefetch of both operands (measured 5-8 % slower on the CLIP shapes)
-      if (bg) launch_w4p<false, false, float, 0, true, true>(p, splits, s, bg);
-      else launch_w4p<false, false, float, 0, false, true>(p, splits, s, bg);
-      return "gemm256_wgrad_splitk";
+    else launch_w4_one<BKM, EPI>(pl.kernel, p, s);
+#endif
+  } else if constexpr (!AK && !BKM) {  // weight gradients, with or without the fused bias gradient
+#ifdef CLIPMI_GEMM_EXPERIMENTS
+    if constexpr (SPLITK) {
+      if (pl.kernel == PF && bg) launch_w4p<AK, BKM, OutT, EPI, true, true>(p, pl.splits, s, bg);
+      else if (pl.kernel == PF) launch_w4p<AK, BKM, OutT, EPI, false, true>(p, pl.splits, s, bg);
+      if (pl.kernel == PF) return true;
     }
 #endif
-    if (bg) launch_w4p<false, false, float, 0, true>(p, splits, s, bg);
-    else launch_w4p<false, false, float, 0, false>(p, splits, s, bg);
-    return "gemm256_wgrad_splitk";
+    if (bg) launch_w4p<AK, BKM, OutT, EPI, true>(p, pl.splits, s, bg);
+    else launch_w4p<AK, BKM, OutT, EPI, false>(p, pl.splits, s, bg);
+  } else {
+    launch_w4p<AK, BKM, OutT, EPI, false>(p, pl.splits, s, nullptr);
   }
-  if (flags != CLIPMI_EPI_BETA) return nullptr;
-  if (bg) launch_w4p<false, false, float, CLIPMI_EPI_BETA, true>(p, 1, s, bg);
-  else launch_w4p<false, false, float, CLIPMI_EPI_BETA, false>(p, 1, s, bg);
-  return "gemm256_wgrad";
+  return true;
+}
+template <int OUT, int EPI, bool W4F>
+bool launch_fp8_w4_row(const GemmPlan& pl, const GemmP& p, hipStream_t s) {
+  if constexpr (W4F) {
+    if (pl.out == OUT && pl.epi == EPI) {
+      launch_w4p8<typename OutOf<OUT>::T, EPI>(p, s);
+      return true;
+    }
+  }
+  return false;
+}
+}  // namespace
+
+void launch_gemm_w4(const GemmPlan& pl, const GemmP& p, hipStream_t s, float* bg) {
+#define ROW(AK, BKM, OUT, EPI, SPLITK, W4F, LABEL) \
+  if (launch_w4_row<AK, BKM, OUT, EPI, SPLITK, W4F>(pl, p, s, bg)) return;
+  CLIPMI_GEMM256_INSTANCES(ROW)
+#undef ROW
+}
+
+void launch_gemm_fp8_w4(const GemmPlan& pl, const GemmP& p, hipStream_t s) {
+#define ROW(OUT, EPI, W4F, LABEL) \
+  if (launch_fp8_w4_row<OUT, EPI, W4F>(pl, p, s)) return;
+  CLIPMI_GEMM_FP8_INSTANCES(ROW)
+#undef ROW
 }
 
 }  // namespace cmg

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "internal.h"
+#include "gemm_plan.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -23,7 +24,7 @@ struct GemmP {
   int k_per_split; float* ws;
   int tiles_n, ntiles;
   int vec;  // all leading dimensions multiples of 4 elements
-  int var;  // 256-kernel main-loop schedule (0 production)
+  int reserved0;  // unused (was the schedule code; the plan names the kernel now): keeps the argument layout
   int vec8; // bf16 C with N, ldc/ldr/ldaux multiples of 8 and C/res/aux/bias 16-B aligned
   int stagger, first_round;  // s_sleep(127) count for half of the first round's workgroups
   const uint8_t* a_scale; const uint8_t* b_scale;  // MXFP8: E8M0 per 32-element k-block, [rows][K/32]
@@ -1043,13 +1044,15 @@ __device__ __forceinline__ void epilogue_q8(const GemmP& p, f32x4 (&acc)[NI][4],
   }
 }
 
-// 4-wave 256x256 kernel (gemm4.hip) for the forward / dgrad layouts; nullptr if not covered
-const char* dispatch_w4(const GemmP& p, hipStream_t s, bool bkm, int flags, int dm);
-// its fp32-output forward form (flags bias, bias + residual, none); nullptr if not covered
-const char* dispatch_w4_f32(const GemmP& p, hipStream_t s, int flags, bool bkm);
-// its persistent weight-gradient form (both operands row-major in k, fp32 out, split-K slabs)
-const char* dispatch_w4_wgrad(const GemmP& p, int splits, hipStream_t s, int flags, float* bg);
-// its MXFP8 form (gemm4.hip gemm_w4p8_kernel); nullptr if the shape or epilogue is not covered
-const char* dispatch_w4_fp8(const GemmP& p, hipStream_t s, bool f32o, bool q8o, int flags);
+// the C++ output type of an instance-list row's `out` column
+template <int OUT> struct OutOf;
+template <> struct OutOf<CLIPMI_F32> { using T = float; };
+template <> struct OutOf<CLIPMI_BF16> { using T = bf16; };
+template <> struct OutOf<CLIPMI_FP8> { using T = uint8_t; };
+
+// gemm4.hip: launch the planned instance of the persistent 4-wave kernels (W4P, W4P_PF and the 4-wave
+// experiments; FP8_W4P).  bg: the fused bias gradient's output when the plan has it.
+void launch_gemm_w4(const GemmPlan& pl, const GemmP& p, hipStream_t s, float* bg);
+void launch_gemm_fp8_w4(const GemmPlan& pl, const GemmP& p, hipStream_t s);
 
 }  // namespace cmg
