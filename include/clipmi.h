@@ -38,7 +38,9 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
  * 6: clipmi_resize_crop_u8 (ragged image batches)
  * 7: clipmi_contrastive_keyed_* (multi-positive contrastive head), clipmi_row_hash64
  * 8: clipmi_group_pick, clipmi_group_count, clipmi_topk_hits (group-aware retrieval evaluation)
- * 9: clipmi_color_u8 (colour augmentation of the input step) */
+ * 9: clipmi_color_u8 (colour augmentation of the input step)
+ * 10: clipmi_gemm_plan
+ * 11: clipmi_sigmoid_pairs, clipmi_sigmoid_reduce (pairwise sigmoid contrastive head) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -556,6 +558,31 @@ int clipmi_contrastive_keyed_bwd_chunk(void* stream, const float* S, const float
 /* out[r] = 64-bit FNV-1a over ids[r][0:N), each token one uint64: h = (h ^ v) * 0x100000001b3 from
  * 0xcbf29ce484222325 ("same caption" as a key, on the device) */
 int clipmi_row_hash64(void* stream, const int64_t* ids, int B, int N, int64_t* out);
+
+/* ---- Pairwise sigmoid contrastive head (csrc/contrastive_sigmoid.hip), fp32 --------------------
+ * Every (text, image) pair of the global batch is one binary problem (Zhai et al. 2023).  A rank scores its B text
+ * rows (global indices label0 + i) against all Bg image rows; S holds the cosines of columns [col0, col0 + C), row
+ * stride C.  With sc = exp(*logit_scale), b = *logit_bias:
+ *   l_ij = sc * s_ij + b
+ *   z_ij = +1 if keys_all[j] == keys_all[label0 + i] (keys_all null: if j == label0 + i), else -1
+ *   loss = norm * sum_ij softplus(-z_ij l_ij)
+ *   u_ij = d loss / d l_ij = -z_ij sigmoid(-z_ij l_ij) norm
+ *   dS_ij = u_ij sc;   d logit_scale = sum_ij u_ij sc s_ij;   d logit_bias = sum_ij u_ij
+ * clipmi_sigmoid_pairs handles one chunk and keeps the row sums rows [B][3] = (sum_j softplus, sum_j u sc s,
+ * sum_j u): col0 == 0 sets them, later chunks add to them.  A materialised block is the chunk C == Bg, col0 == 0.
+ * logits (null, or [B][C]) receives l; dS (null, or [B][C]; may be S itself) receives dS.  dS == null is the no-grad
+ * form: only rows[.][0] is formed and rows[.][1:3] are left as they are.  softplus and sigmoid go through
+ * exp(-|x|) alone, so any finite logit gives finite outputs.  keys_all null and all-distinct keys give the same bits.
+ * Guards: logit_bias, rows non-null; 0 <= label0, label0 + B <= Bg; the chunk inside [0, Bg); B = 0 returns.
+ * clipmi_sigmoid_reduce sums rows [n][3] over n in a fixed tree: loss[0] = norm * sum_0; dls[0] = g * sum_1 and
+ * db[0] = g * sum_2 with g = *gscale (null: 1), set (beta = 0) or accumulated (beta = 1, e.g. straight into the
+ * gradient arenas).  Each of loss, dls, db may be null (not all three); with dls and db both null columns 1, 2 of
+ * rows are not read.  n = 1 scales and accumulates sums that are already reduced. */
+int clipmi_sigmoid_pairs(void* stream, const float* S, const float* logit_scale, const float* logit_bias,
+                         const int64_t* keys_all, int B, int C, int col0, int Bg, int label0, float norm,
+                         float* logits, float* dS, float* rows);
+int clipmi_sigmoid_reduce(void* stream, const float* rows, int n, float norm, const float* gscale, float* loss,
+                          float* dls, float* db, int beta);
 
 /* ---- Optimizer (trainer.py:95,98; [HF] optimization.py:101-129) ------------------------------ */
 int64_t clipmi_grad_norm_ws(void);

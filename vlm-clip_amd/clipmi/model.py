@@ -18,6 +18,11 @@ checkpoint format and error types as the reference; the compute runs on libclipm
                through torch, or gloo) or a clipmi.comm.Communicator (RCCL issued by libclipmi)
   forward(..., pair_keys=...)  one integer key per pair: pairs with equal keys are positives of each other in the
                loss (multi-positive InfoNCE, clipmi.losses); None is the reference's diagonal loss
+  loss         "softmax" (default: the reference's symmetric InfoNCE, plain or keyed) or "sigmoid" (the pairwise
+               sigmoid loss of Zhai et al. 2023, towers.SigmoidContrastiveFn: every pair of the global batch one
+               binary problem, so any number of positives per row is the ordinary case).  "sigmoid" adds one
+               parameter, sigmoid_head.logit_bias (logit_bias_init, default -10); the temperature stays
+               clip.logit_scale and is trainable exactly when it is under "softmax": frozen with freeze_clip=True
 """
 from __future__ import annotations
 
@@ -32,7 +37,7 @@ from . import config as C
 from . import synth
 from . import towers as T
 from .losses import as_pair_keys
-from .modules import AdapterParams, CLIPParams
+from .modules import AdapterParams, CLIPParams, SigmoidHeadParams
 
 
 class _Runtime:
@@ -85,7 +90,8 @@ class CLIPWithAdapters(nn.Module):
     def __init__(self, clip_model_name="openai/clip-vit-base-patch32", text_adapter_size=256,
                  vision_adapter_size=256, shared_adapter_layers=2, freeze_clip=True, use_text_adapter=True,
                  use_vision_adapter=True, use_shared_adapters=True, *, device=None, precision="bf16",
-                 pooling="first", init_seed=0, process_group=None, fast_init=False, residual_fp32=None):
+                 pooling="first", init_seed=0, process_group=None, fast_init=False, residual_fp32=None,
+                 loss="softmax", logit_bias_init=-10.0):
         super().__init__()
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -95,11 +101,14 @@ class CLIPWithAdapters(nn.Module):
             raise ValueError("precision='fp8' runs the frozen towers only (MXFP8 forward GEMMs); use freeze_clip=True")
         if pooling not in ("first", "eos"):
             raise ValueError("pooling must be 'first' or 'eos'")
+        if loss not in ("softmax", "sigmoid"):
+            raise ValueError("loss must be 'softmax' or 'sigmoid'")
         cfg = C.resolve(clip_model_name)
         self.config = cfg
         self.precision = precision
         self.pooling = pooling
         self.process_group = process_group
+        self.loss = loss
         exact = precision in ("fp32", "bf16x3")  # fp32 activations and weights (no bf16 shadow)
         dtype = torch.float32 if exact else torch.bfloat16
         shadow = not exact
@@ -132,6 +141,10 @@ class CLIPWithAdapters(nn.Module):
             self.shared_adapters = nn.ModuleList([SharedAdapterParams(text_hidden, vision_hidden, device,
                                                                       seed=init_seed, prefix=f"shared_adapters.{i}")
                                                   for i in range(shared_adapter_layers)])
+        if loss == "sigmoid":
+            # its own one-parameter arena: the clip arena, its layout and its state-dict keys stay as they are.
+            # logit_scale remains CLIP's (frozen with freeze_clip=True); the bias trains with the adapters
+            self.sigmoid_head = SigmoidHeadParams(device, logit_bias_init)
         self._rt = _Runtime(self.clip, dtype)
         self._rt.fp8 = precision == "fp8"
         # bf16 mode: the towers' residual stream in fp32 (engine resid_f32; profiles/r05_bf16_error_sources.log),
@@ -196,6 +209,8 @@ class CLIPWithAdapters(nn.Module):
                 out.append(a.arena)
         for a in (self.shared_adapters or []):
             out.append(a.arena)
+        if self.loss == "sigmoid":
+            out.append(self.sigmoid_head.arena)
         return out
 
     # ------------------------------------------------------------------ features
@@ -319,7 +334,9 @@ class CLIPWithAdapters(nn.Module):
         """model_m.py:127-176.  pair_keys (extension): one integer key per pair of this rank's batch (an int32 /
         int64 tensor or a sequence of ints of length B); pairs of the global batch with equal keys are each other's
         positives in the loss (towers.KeyedContrastiveFn; clipmi.losses builds keys from captions or class names).
-        None: the reference's diagonal loss.  The logits outputs do not depend on it."""
+        None: the reference's diagonal loss.  The logits outputs do not depend on it.  Under loss="sigmoid" the same
+        keys say which pairs are positive (towers.SigmoidContrastiveFn); logits_per_text then carries the bias, and
+        logits_per_image is its transpose on one device and None in a group (there is no image->text block)."""
         keys = None
         if pair_keys is not None and return_loss and input_ids is not None and pixel_values is not None:
             keys = as_pair_keys(pair_keys, len(input_ids), self.clip.arena.device)
@@ -333,6 +350,13 @@ class CLIPWithAdapters(nn.Module):
             image_features = self.get_image_features(pixel_values) if pixel_values is not None else None
         if return_loss and text_features is not None and image_features is not None:
             group = self.process_group
+            if self.loss == "sigmoid":
+                loss, t, i, lpt = T.sigmoid_contrastive(text_features, image_features, self.clip.logit_scale,
+                                                        self.sigmoid_head.logit_bias, keys, group, True,
+                                                        self.clip.arena, self.sigmoid_head.arena)
+                one = CM.world_rank(group)[0] == 1 and lpt is not None
+                return {"loss": loss, "text_features": t, "image_features": i, "logits_per_text": lpt,
+                        "logits_per_image": lpt.t() if one else None}
             if keys is not None:
                 loss, t, i, lpt, lpi = T.KeyedContrastiveFn.apply(text_features, image_features, self.clip.logit_scale,
                                                                   keys, group, True, self.clip.arena)
@@ -374,6 +398,8 @@ class CLIPWithAdapters(nn.Module):
                                                      for k, v in self.shared_adapters.state_dict().items()}
         if not adapter_state_dict:
             raise ValueError("No adapters enabled to save")
+        if self.loss == "sigmoid":
+            adapter_state_dict["sigmoid_head"] = {k: v.detach().clone() for k, v in self.sigmoid_head.state_dict().items()}
         d = os.path.dirname(save_path)
         if d:  # the reference calls os.makedirs("") for bare file names and crashes
             os.makedirs(d, exist_ok=True)
@@ -404,6 +430,12 @@ class CLIPWithAdapters(nn.Module):
             self.shared_adapters.load_state_dict(adapter_state_dict["shared_adapters"])
         elif self.use_shared_adapters:
             raise ValueError("Shared adapters are enabled but no weights found in checkpoint")
+        if "sigmoid_head" in adapter_state_dict:
+            if self.loss != "sigmoid":
+                raise ValueError("Sigmoid head weights found but the sigmoid loss is not enabled")
+            self.sigmoid_head.load_state_dict(adapter_state_dict["sigmoid_head"])
+        elif self.loss == "sigmoid":
+            raise ValueError("Sigmoid loss is enabled but no sigmoid head weights found in checkpoint")
         print(f"Adapter weights loaded from {load_path}")
         print(f"Loaded adapters: {list(adapter_state_dict.keys())}")
 

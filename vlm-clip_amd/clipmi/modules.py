@@ -136,3 +136,13 @@ class AdapterParams(ArenaModule):
     def __init__(self, hidden, bottleneck, device, ln=True, shadow=True, names=("down_project", "up_project")):
         super().__init__(adapter_specs(hidden, bottleneck, ln, names), device, shadow)
         self.hidden, self.bottleneck, self.has_ln, self.names = hidden, bottleneck, ln, names
+
+
+class SigmoidHeadParams(ArenaModule):
+    """The pairwise sigmoid loss's one parameter of its own, logit_bias (Zhai et al. 2023 start it at -10: at
+    initialisation nearly every pair is a negative); the temperature stays CLIPParams.logit_scale.  Read in fp32."""
+
+    def __init__(self, device, logit_bias_init=-10.0):
+        super().__init__([("logit_bias", ())], device, shadow=False)
+        with torch.no_grad():
+            self.logit_bias.fill_(float(logit_bias_init))

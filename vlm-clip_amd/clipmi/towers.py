@@ -18,6 +18,7 @@ Reference mapping:
   PoolProjFn     <- [:, 0, :] + text_projection / visual_projection (model_m.py:102-103, 122-123)
   ContrastiveFn  <- model_m.py:146-171 (+ the SURVEY §8e data-parallel all-gather form)
   KeyedContrastiveFn  the same with the positives of a row given by a key per pair (no reference counterpart)
+  SigmoidContrastiveFn  the pairwise sigmoid loss over the same features and keys (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -184,6 +185,9 @@ _lib.declare("clipmi_contrastive_keyed_finish", [c_vp, c_vp, c_int, c_vp, c_vp, 
 _lib.declare("clipmi_contrastive_keyed_bwd_chunk", [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                                     c_int, c_int, c_float, c_vp, c_vp, c_int])
 _lib.declare("clipmi_row_hash64", [c_vp, c_vp, c_int, c_int, c_vp])
+_lib.declare("clipmi_sigmoid_pairs", [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_float, c_vp,
+                                      c_vp, c_vp])
+_lib.declare("clipmi_sigmoid_reduce", [c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_int])
 _lib.declare("clipmi_cast_f32_bf16", [c_vp, c_vp, c_vp, c_i64])
 _lib.declare("clipmi_grad_norm_ws", [], c_i64)
 _lib.declare("clipmi_grad_norm", [c_vp, c_vp, c_i64, c_float, c_vp, c_vp, c_i64])
@@ -1125,3 +1129,128 @@ class KeyedContrastiveFn(ContrastiveFn):
         if keys.dtype != torch.int64 or keys.dim() != 1 or keys.shape[0] != tf.shape[0] or keys.device != tf.device:
             raise ValueError(f"pair keys must be an int64 tensor of length {tf.shape[0]} on the features' device")
         return ContrastiveFn.run(ctx, tf, imf, logit_scale, group, global_loss, arena, keys.contiguous())
+
+
+def _sigmoid_chunks(s, x_local, y_all, ls, lb, keys, lab0, norm, C, rows, logits, dx_local, dy_all):
+    """The one pass of the sigmoid head over column chunks of width C (C = Bg: the materialised block).  Per chunk:
+    the cosines x_local y_all[c0:]^T, clipmi_sigmoid_pairs (row sums into rows [B, 3]; logits [B, Bg] only with one
+    chunk) and, when dx_local / dy_all are given, dS written over the cosines, dy_all[c0:] = dS^T x_local (column
+    direction, every chunk writes its own rows) and dx_local (+)= dS y_all[c0:] (row direction, summed over the
+    chunks): three GEMMs per chunk, one without the gradients."""
+    B, E = x_local.shape
+    Bg = y_all.shape[0]
+    grad = dx_local is not None
+    sbuf = torch.empty(B * min(C, Bg), dtype=torch.float32, device=x_local.device)
+    for n, c0 in enumerate(range(0, Bg, C)):
+        cw = min(C, Bg - c0)
+        _gemm_f32(B, cw, E, x_local, E, True, y_all[c0:], E, True, sbuf, cw)
+        call("clipmi_sigmoid_pairs", s, P_(sbuf), P_(ls), P_(lb), P_(keys), B, cw, c0, Bg, lab0, norm, P_(logits),
+             P_(sbuf) if grad else None, P_(rows))
+        if grad:
+            _gemm_f32(cw, E, B, sbuf, cw, False, x_local, E, False, dy_all[c0:], E)
+            _gemm_f32(B, E, cw, sbuf, cw, True, y_all[c0:], E, False, dx_local, E, flags=_lib.EPI_BETA if n else 0)
+
+
+class SigmoidContrastiveFn(torch.autograd.Function):
+    """Pairwise sigmoid contrastive loss (Zhai et al. 2023; csrc/contrastive_sigmoid.hip): every (text, image) pair
+    of the global batch is one binary problem, positive when the keys are equal (keys None: on the diagonal),
+        loss = (1 / Bg) sum_ij softplus(-z_ij (exp(logit_scale) <t^_i, i^_j> + logit_bias)).
+    Each rank scores its B text rows against all Bg images (label offset rank * B), so the ranks together cover
+    every pair once: only the image features (and the keys) are all-gathered, there is no image->text block, and
+    d i^_all = dS^T t^ is reduce-scattered to its owners while d t^ = dS i^_all stays local.
+
+    A pair's gradient depends on nothing but the pair, so the whole head is ONE pass over the score block: per chunk
+    (the whole block when Bg <= contrastive_chunk()) the score GEMM, clipmi_sigmoid_pairs writing dS over the scores,
+    and the two gradient GEMMs -- three GEMMs where the softmax head runs four per direction (two passes over two
+    blocks).  What is saved for backward are the two l2norm states, d t^, d i^_all and the two scalar gradients,
+    all for a unit upstream gradient; backward scales them by the incoming gradient on the device.  No [B, Bg] tensor
+    lives between forward and backward.  need False (no_grad, or nothing requires grad): the score GEMM and the
+    loss half of the kernel alone.  Returns (loss, t^, i^, logits_per_text); the last is None in the streamed form.
+    Call it through sigmoid_contrastive(), which works out need."""
+
+    @staticmethod
+    def forward(ctx, tf, imf, logit_scale, logit_bias, keys, group, global_loss, arena, bias_arena, need):
+        if keys is not None and (keys.dtype != torch.int64 or keys.dim() != 1 or keys.shape[0] != tf.shape[0]
+                                 or keys.device != tf.device):
+            raise ValueError(f"pair keys must be an int64 tensor of length {tf.shape[0]} on the features' device")
+        world, rank = CM.world_rank(group)
+        B, E = tf.shape
+        dev = tf.device
+        s = K.stream()
+        t = tf.to(torch.float32).contiguous()
+        i = imf.to(torch.float32).contiguous()
+        th, ih = torch.empty_like(t), torch.empty_like(i)
+        tn = torch.empty(B, dtype=torch.float32, device=dev)
+        inn = torch.empty(B, dtype=torch.float32, device=dev)
+        call("clipmi_l2norm_fwd", s, P_(t), P_(th), P_(tn), B, E)
+        call("clipmi_l2norm_fwd", s, P_(i), P_(ih), P_(inn), B, E)
+        ig = _gather(ih, group, world)
+        kg = _gather_keys(keys.contiguous(), group, world) if keys is not None else None  # rank order, as the features
+        Bg = ig.shape[0]
+        C = min(contrastive_chunk(world), Bg)
+        ls = logit_scale.detach().reshape(1)
+        lb = logit_bias.detach().to(torch.float32).reshape(1)
+        lab0, norm = rank * B, 1.0 / Bg
+        rows = torch.empty(B, 3, dtype=torch.float32, device=dev)
+        lt = torch.empty(B, Bg, dtype=torch.float32, device=dev) if C == Bg else None
+        dth = dIg = None
+        if need:
+            dth = torch.empty(B, E, dtype=torch.float32, device=dev)
+            dIg = torch.empty(Bg, E, dtype=torch.float32, device=dev)
+        _sigmoid_chunks(s, th, ig, ls, lb, kg, lab0, norm, C, rows, lt, dth, dIg)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        # (unused, d logit_scale, d logit_bias) for a unit upstream gradient, laid out as one row of `rows`
+        red = torch.zeros(3, dtype=torch.float32, device=dev)
+        call("clipmi_sigmoid_reduce", s, P_(rows), B, norm, None, P_(loss), P_(red[1:]) if need else None,
+             P_(red[2:]) if need else None, 0)
+        loss_out = loss
+        if world > 1 and global_loss:
+            loss_out = CM.all_reduce_(loss.clone(), group)
+        if need:
+            # the outputs th, ih must go through save_for_backward (see ContrastiveFn.run)
+            ctx.save_for_backward(th, ih, tn, inn, dth, dIg, red)
+            ctx.group, ctx.world = group, world
+            ctx.ls_param, ctx.lb_param, ctx.arena, ctx.bias_arena = logit_scale, logit_bias, arena, bias_arena
+        if lt is not None:
+            ctx.mark_non_differentiable(lt)
+        return loss_out, th, ih, lt
+
+    @staticmethod
+    def backward(ctx, gloss, gth, gih, glt):
+        th, ih, tn, inn, dth1, dIg1, red = ctx.saved_tensors
+        B, E = th.shape
+        dev = th.device
+        s = K.stream()
+        gl = (gloss.to(torch.float32).contiguous().reshape(1) if gloss is not None
+              else torch.zeros(1, dtype=torch.float32, device=dev))
+        dih = _reduce_scatter(dIg1 * gl, ctx.group, ctx.world)
+        dth = dth1 * gl
+        if gth is not None:
+            dth += gth
+        if gih is not None:
+            dih += gih
+        want_ls, want_lb = ctx.ls_param.requires_grad, ctx.lb_param.requires_grad
+        if want_ls or want_lb:
+            # both scalars accumulate straight into their grad arenas; all ranks' shares are summed by the
+            # data-parallel gradient all-reduce
+            if want_ls:
+                ctx.arena.prepare_grads()
+            if want_lb:
+                ctx.bias_arena.prepare_grads()
+            call("clipmi_sigmoid_reduce", s, P_(red), 1, 1.0, P_(gl), None,
+                 ctx.arena.ptr("logit_scale", ctx.arena.grad) if want_ls else None,
+                 ctx.bias_arena.ptr("logit_bias", ctx.bias_arena.grad) if want_lb else None, 1)
+        dt = torch.empty(B, E, dtype=torch.float32, device=dev)
+        di = torch.empty(B, E, dtype=torch.float32, device=dev)
+        call("clipmi_l2norm_bwd", s, P_(dth), P_(th), P_(tn), P_(dt), B, E)
+        call("clipmi_l2norm_bwd", s, P_(dih), P_(ih), P_(inn), P_(di), B, E)
+        return (dt, di) + (None,) * 8
+
+
+def sigmoid_contrastive(tf, imf, logit_scale, logit_bias, keys=None, group=None, global_loss=True, arena=None,
+                        bias_arena=None):
+    """SigmoidContrastiveFn with need worked out here (a Function's forward runs with grad mode off and cannot tell):
+    gradients are formed when grad mode is on and a feature set or a loss parameter requires grad."""
+    need = torch.is_grad_enabled() and any(x.requires_grad for x in (tf, imf, logit_scale, logit_bias))
+    return SigmoidContrastiveFn.apply(tf, imf, logit_scale, logit_bias, keys, group, global_loss, arena, bias_arena,
+                                      need)

@@ -244,7 +244,8 @@ def _to_device(batch, device, non_blocking):
 class CLIPAdapterTrainer:
     """trainer.py:11-167.  ``trainable="adapter"`` selects parameters whose name contains
     "adapter" exactly like trainer.py:40-43; ``trainable="requires_grad"`` takes every
-    parameter with requires_grad (full fine-tune).
+    parameter with requires_grad (full fine-tune).  Under the model's loss="sigmoid" the adapter
+    mode also takes sigmoid_head.logit_bias, the loss's own parameter (it exists under that loss only).
 
     ``positives`` (no reference counterpart) chooses the positives of the contrastive loss in train_step and
     evaluate(): None, the reference's diagonal loss; "caption", pairs whose token rows are equal (hashed on the
@@ -273,7 +274,7 @@ class CLIPAdapterTrainer:
         self.trainable_params = []
         for name, param in model.named_parameters():
             if trainable == "adapter":
-                if "adapter" in name or "shared_adapters" in name:
+                if "adapter" in name or "shared_adapters" in name or name == "sigmoid_head.logit_bias":
                     self.trainable_params.append(param)
             elif param.requires_grad:
                 self.trainable_params.append(param)
