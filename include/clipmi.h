@@ -40,7 +40,8 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
  * 8: clipmi_group_pick, clipmi_group_count, clipmi_topk_hits (group-aware retrieval evaluation)
  * 9: clipmi_color_u8 (colour augmentation of the input step)
  * 10: clipmi_gemm_plan
- * 11: clipmi_sigmoid_pairs, clipmi_sigmoid_reduce (pairwise sigmoid contrastive head) */
+ * 11: clipmi_sigmoid_pairs, clipmi_sigmoid_reduce (pairwise sigmoid contrastive head)
+ * 12: clipmi_affine_u8 (affine / rotation augmentation of the input step) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -326,6 +327,43 @@ typedef struct clipmi_color_item {
 int64_t clipmi_color_u8_ws(const clipmi_color_item* items, int B, int H, int W);
 int clipmi_color_u8(void* stream, uint8_t* images /* [B,H,W,3], in place */, const clipmi_color_item* items,
                     int B, int H, int W, void* ws, int64_t ws_bytes);
+/* Geometric augmentation (csrc/affine.hip; clipmi_version() >= 12): PIL's Image.transform(size, AFFINE, m, NEAREST |
+ * BILINEAR, fillcolor=...) bit for bit, which is what torchvision's RandomAffine / RandomRotation do to a PIL image:
+ * src uint8 [B, H, W, 3] -> dst of the same shape, image b through items[b].  It runs on clipmi_resize_crop_u8's
+ * output and in front of clipmi_color_u8.  m = (a0..a5) maps an output pixel to a source coordinate; every output
+ * byte is written, with a sampled value or with the fill colour.  All coefficient arithmetic is IEEE double, each
+ * operation rounded on its own (no fma).  For output pixel (x, y):
+ *   bilinear (filter 1; PIL affine_transform + bilinear_filter32RGB):
+ *     xin = x + 0.5, yin = y + 0.5; xo = (a0 xin + a1 yin) + a2; yo = (a3 xin + a4 yin) + a5;
+ *     xo < 0 or xo >= W or yo < 0 or yo >= H: the fill.  Else xo -= 0.5, yo -= 0.5, xi = floor(xo), yi = floor(yo),
+ *     dx = xo - xi, dy = yo - yi; x0 = clamp(xi, 0, W - 1), x1 = clamp(xi + 1, 0, W - 1), row = clamp(yi, 0, H - 1);
+ *     per channel v1 = p[row][x0] + (p[row][x1] - p[row][x0]) dx (the difference an integer); v2 the same on row
+ *     yi + 1 when 0 <= yi + 1 < H, else v2 = v1; v = v1 + (v2 - v1) dy; the byte is trunc(v), inside [0, 255].
+ *   nearest (filter 0) with a1 != 0 or a3 != 0 (PIL affine_fixed, 16.16 fixed point, 32-bit integers):
+ *     FIX(v) = floor(v * 65536.0 + 0.5); A0 = FIX(a0), A1 = FIX(a1), A3 = FIX(a3), A4 = FIX(a4),
+ *     A2 = FIX((a2 + a0 * 0.5) + a1 * 0.5), A5 = FIX((a5 + a3 * 0.5) + a4 * 0.5); the source pixel is
+ *     ((A2 + A0 x + A1 y) >> 16, (A5 + A3 x + A4 y) >> 16), arithmetic shifts; outside the image: the fill.
+ *   nearest with a1 == 0 and a3 == 0 exactly (PIL ImagingScaleAffine): a column table from a running double sum,
+ *     xo = a2 + a0 * 0.5; for x = 0 .. W - 1: xtab[x] = xo < 0 ? -1 : (int)xo, xo += a0; a row table likewise from
+ *     a5 + a4 * 0.5 and a4; the output is src[ytab[y]][xtab[x]] when both entries are inside the image, else the
+ *     fill.  The running sum is not a2 + a0 (x + 0.5), and that closed form changes bytes.
+ * The identity (1, 0, 0, 0, 1, 0) copies the image under either filter.  `items` is host memory: every item is
+ * validated before any launch (a non-finite coefficient, a filter outside {0, 1}, a fill outside 0..0xFFFFFF, and,
+ * for either coefficient row (a, b, c), |a| W + |b| H + |c| >= 16384 -- below that bound PIL's 32-bit fixed point
+ * cannot overflow: 16384 * 65536 = 2^30 -- return CLIPMI_ERR_INVALID naming the item; so do H or W outside 1..4096
+ * and src and dst that overlap).  The fixed-point integers are derived on the host and uploaded with the per-image
+ * records into the workspace on the stream, in one copy; the kernels read that copy and src only.  One launch whatever
+ * B is, plus a pre-pass (one thread per image and axis) that fills the tables behind the records when some item takes
+ * the third path; no host synchronisation.  B == 0 returns.  clipmi_affine_u8_ws returns the workspace bytes (a
+ * negative status on invalid items); the workspace must be 16-byte aligned. */
+typedef struct clipmi_affine_item {
+  double  m[6];     /* output pixel -> source coordinate, PIL's AFFINE data (a0..a5) */
+  int32_t filter;   /* 0 nearest, 1 bilinear */
+  int32_t fill;     /* 0xRRGGBB, the colour where no source pixel is hit */
+} clipmi_affine_item;
+int64_t clipmi_affine_u8_ws(const clipmi_affine_item* items, int B, int H, int W);
+int clipmi_affine_u8(void* stream, const uint8_t* src, uint8_t* dst, const clipmi_affine_item* items, int B, int H,
+                     int W, void* ws, int64_t ws_bytes);
 /* pooled token per row: mode 0 first token (model_m.py:102), 1 first EOS (0 when the row has none), 2 argmax id,
  * the first of tied maxima ([HF] :561-581).  gather: out[b] = src[b*S + idx[b]]; scatter: dst[b*S + idx[b]] (+)=
  * src[b], the other rows of dst untouched; idx NULL: token 0.  B = 0 is a no-op. */

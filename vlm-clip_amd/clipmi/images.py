@@ -21,7 +21,16 @@ Colour: ``color_jitter_u8`` runs torchvision's ColorJitter / RandomGrayscale as 
 [B, H, W, 3] in place, each image with its own factors and op order (include/clipmi.h clipmi_color_u8: two
 launches whatever B is).  ``ColorJitter`` samples the per-image records as ColorJitter.get_params does;
 an ``ImageBatch`` that carries records (``with_color``) gets them applied by ``preprocess`` after the
-resize, the window and the flip."""
+resize, the window and the flip.
+
+Geometry: ``affine_u8`` is PIL's ``Image.transform(size, AFFINE, m, NEAREST | BILINEAR, fillcolor=...)`` bit for
+bit on uint8 [B, H, W, 3], each image with its own matrix, filter and fill (include/clipmi.h clipmi_affine_u8: one
+launch whatever B is), which is what torchvision's RandomAffine / RandomRotation do to a PIL image.
+``rotation_matrix`` is Image.rotate's matrix, ``affine_matrix`` torchvision's published inverse affine matrix;
+``RandomAffine`` / ``RandomRotation`` sample per-image ``AffineItem`` records as their ``get_params`` do.  An
+``ImageBatch`` that carries them (``with_affine``) gets them applied by ``preprocess`` after the resize, the window
+and the flip and in front of the colour records: Compose([RandomResizedCrop, RandomHorizontalFlip, RandomAffine,
+ColorJitter])."""
 from __future__ import annotations
 
 import ctypes
@@ -73,6 +82,55 @@ class ColorItem(ctypes.Structure):
 
 
 COLOR_OPS = {"brightness": 1, "contrast": 2, "saturation": 3, "hue": 4}
+AFFINE_FILTERS = {"nearest": 0, "bilinear": 1}
+
+
+def _fill_code(who, fill):
+    """A fill colour, an int (gray) or an (r, g, b) triple of bytes, as 0xRRGGBB."""
+    if isinstance(fill, (tuple, list)):
+        rgb = tuple(fill)
+    elif isinstance(fill, (int, float)):
+        rgb = (fill,) * 3
+    else:
+        rgb = ()
+    if len(rgb) != 3 or not all(isinstance(v, (int, float)) and v == int(v) and 0 <= v <= 255 for v in rgb):
+        raise ValueError(f"{who}: fill must be an int in 0..255 or an (r, g, b) triple of them, got {fill!r}")
+    r, g, b = (int(v) for v in rgb)
+    return r << 16 | g << 8 | b
+
+
+def _filter_code(who, interpolation):
+    if interpolation not in AFFINE_FILTERS:
+        raise ValueError(f"{who}: interpolation must be one of {sorted(AFFINE_FILTERS)}, got {interpolation!r}")
+    return AFFINE_FILTERS[interpolation]
+
+
+class AffineItem(ctypes.Structure):
+    """include/clipmi.h clipmi_affine_item.  ``AffineItem.of`` builds one from a matrix."""
+    _fields_ = [("m", ctypes.c_double * 6), ("filter", ctypes.c_int32), ("fill", ctypes.c_int32)]
+
+    @classmethod
+    def of(cls, matrix, interpolation="nearest", fill=0):
+        """matrix: (a0..a5), output pixel -> source coordinate, PIL's AFFINE data; interpolation: "nearest" |
+        "bilinear"; fill: the colour where no source pixel is hit, an int (gray) or an (r, g, b) triple."""
+        m = [float(v) for v in matrix]
+        if len(m) != 6:
+            raise ValueError(f"AffineItem.of: the matrix has six coefficients, got {len(m)}")
+        return cls((ctypes.c_double * 6)(*m), _filter_code("AffineItem.of", interpolation), _fill_code("AffineItem.of", fill))
+
+    @property
+    def matrix(self):
+        return list(self.m)
+
+    @property
+    def interpolation(self):
+        return {v: k for k, v in AFFINE_FILTERS.items()}[self.filter]
+
+    def is_identity(self):
+        return self.matrix == AFFINE_IDENTITY
+
+
+AFFINE_IDENTITY = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0]
 
 _lib.declare("clipmi_resize_crop_u8_ws", [ctypes.POINTER(ImageItem), ctypes.c_int, ctypes.c_int, ctypes.c_int],
              ctypes.c_int64)
@@ -83,6 +141,10 @@ _lib.declare("clipmi_color_u8_ws", [ctypes.POINTER(ColorItem), ctypes.c_int, cty
              ctypes.c_int64)
 _lib.declare("clipmi_color_u8", [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ColorItem), ctypes.c_int,
                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64])
+_lib.declare("clipmi_affine_u8_ws", [ctypes.POINTER(AffineItem), ctypes.c_int, ctypes.c_int, ctypes.c_int],
+             ctypes.c_int64)
+_lib.declare("clipmi_affine_u8", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(AffineItem),
+                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64])
 
 
 class ImageBatch:
@@ -91,9 +153,10 @@ class ImageBatch:
     ``data``: uint8 [sum h*w*3] (host, pinned when CUDA is available, or device after ``.to``);
     ``sizes``: [(h, w)]; ``offsets``: byte offset of each image; ``boxes``: [(x0, y0, cw, ch)] (default:
     the whole image); ``flips``: [0 | 1] (default 0); ``mode``: "processor" | "square"; ``color``: one ColorItem
-    per image, applied to ``preprocess``'s output (default None: no colour pass)."""
+    per image, applied to ``preprocess``'s output (default None: no colour pass); ``affine``: one AffineItem per
+    image, applied after the resize, the window and the flip and in front of ``color`` (default None: no such pass)."""
 
-    def __init__(self, data, sizes, offsets, boxes=None, flips=None, mode="processor", color=None):
+    def __init__(self, data, sizes, offsets, boxes=None, flips=None, mode="processor", color=None, affine=None):
         if mode not in MODES:
             raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
         self.data = data
@@ -106,6 +169,10 @@ class ImageBatch:
         self.color = None if color is None else list(color)
         if self.color is not None and len(self.color) != n:
             raise ValueError("ImageBatch: color must have one ColorItem per image")
+        self.affine = None if affine is None else list(affine)
+        if self.affine is not None and (len(self.affine) != n or
+                                        not all(isinstance(it, AffineItem) for it in self.affine)):
+            raise ValueError("ImageBatch: affine must have one AffineItem per image")
         if not (len(self.offsets) == len(self.boxes) == len(self.flips) == n):
             raise ValueError("ImageBatch: sizes, offsets, boxes and flips must have one entry per image")
         if any(len(b) != 4 for b in self.boxes):
@@ -134,7 +201,7 @@ class ImageBatch:
 
     def _like(self, **kw):
         a = dict(data=self.data, sizes=self.sizes, offsets=self.offsets, boxes=self.boxes, flips=self.flips,
-                 mode=self.mode, color=self.color)
+                 mode=self.mode, color=self.color, affine=self.affine)
         a.update(kw)
         return ImageBatch(**a)
 
@@ -160,6 +227,9 @@ class ImageBatch:
     def with_color(self, items):
         return self._like(color=items)
 
+    def with_affine(self, items):
+        return self._like(affine=items)
+
     def items(self):
         """The clipmi_image_item table (host)."""
         arr = (ImageItem * max(len(self), 1))()
@@ -170,8 +240,10 @@ class ImageBatch:
 
 def preprocess(batch, image_size, mode=None, out=None):
     """ImageBatch (on the GPU) -> uint8 [B, S, S, 3] on its device, through clipmi_resize_crop_u8.  mode: the
-    batch's own when None.  out: a contiguous uint8 view of B*S*S*3 elements to write into.  A batch with colour
-    records (``with_color``) gets them applied to the output in place (clipmi_color_u8, two more launches)."""
+    batch's own when None.  out: a contiguous uint8 view of B*S*S*3 elements to write into.  A batch with affine
+    records (``with_affine``) has the resize write a scratch [B, S, S, 3] and clipmi_affine_u8 write the output (one
+    more launch); a batch with colour records (``with_color``) then gets them applied to the output in place
+    (clipmi_color_u8, two more launches)."""
     mode = batch.mode if mode is None else mode
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
@@ -189,9 +261,12 @@ def preprocess(batch, image_size, mode=None, out=None):
         elif out.dtype != torch.uint8 or out.numel() != B * S * S * 3 or not out.is_contiguous():
             raise ValueError("preprocess: out must be a contiguous uint8 view of B*S*S*3 elements")
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=batch.data.device)
-        _lib.check(L.clipmi_resize_crop_u8(K.stream(), K.ptr(batch.data), batch.data.numel(), items, B, K.ptr(out), S,
-                                           MODES[mode], K.ptr(ws), nb), "clipmi_resize_crop_u8")
+        resized = out if batch.affine is None else torch.empty(B, S, S, 3, dtype=torch.uint8, device=batch.data.device)
+        _lib.check(L.clipmi_resize_crop_u8(K.stream(), K.ptr(batch.data), batch.data.numel(), items, B, K.ptr(resized),
+                                           S, MODES[mode], K.ptr(ws), nb), "clipmi_resize_crop_u8")
     out = out.view(B, S, S, 3)
+    if batch.affine is not None:
+        affine_u8(resized, batch.affine, out=out)
     if batch.color is not None:
         color_jitter_u8(out, batch.color)
     return out
@@ -228,6 +303,83 @@ def color_jitter_u8(images, items):
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=images.device)
         _lib.check(L.clipmi_color_u8(K.stream(), K.ptr(images), table, B, H, W, K.ptr(ws), nb), "clipmi_color_u8")
     return images
+
+
+def _affine_table(items):
+    """An AffineItem sequence as the ctypes array the library takes."""
+    n = len(items)
+    if not all(isinstance(it, AffineItem) for it in items):
+        raise ValueError("affine records must be AffineItem (AffineItem.of, RandomAffine.sample)")
+    return (AffineItem * max(n, 1))(*items), n
+
+
+def affine_u8(images, items, out=None):
+    """uint8 [B, H, W, 3] on the GPU through clipmi_affine_u8: image b through items[b]'s matrix, filter and fill.
+    Returns a new tensor, or ``out`` (uint8 [B, H, W, 3], contiguous, on the same device, no byte shared with
+    ``images``).  ``images`` is left as it is."""
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("affine_u8: images must be uint8 [B, H, W, 3]")
+    if not images.is_cuda:
+        raise ValueError("affine_u8 needs the images on the GPU; there is no CPU fallback")
+    if not images.is_contiguous():
+        raise ValueError("affine_u8: images must be contiguous")
+    B, H, W = (int(v) for v in images.shape[:3])
+    table, n = _affine_table(items)
+    if n != B:
+        raise ValueError(f"affine_u8: {n} records for {B} images")
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(images.shape)
+                or not out.is_contiguous() or out.device != images.device):
+            raise ValueError("affine_u8: out must be a contiguous uint8 tensor of images' shape on images' device")
+        lo, hi, nbytes = images.data_ptr(), out.data_ptr(), images.numel()
+        if nbytes and lo < hi + nbytes and hi < lo + nbytes:
+            raise ValueError("affine_u8: out must not alias images (every output pixel gathers from the source image)")
+    L = _lib.lib()
+    nb = int(L.clipmi_affine_u8_ws(table, B, max(H, 1) if B == 0 else H, max(W, 1) if B == 0 else W))
+    if nb < 0:
+        _lib.check(nb, "clipmi_affine_u8_ws")
+    with torch.cuda.device(images.device):
+        if out is None:
+            out = torch.empty_like(images)
+        if B == 0:
+            return out
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=images.device)
+        _lib.check(L.clipmi_affine_u8(K.stream(), K.ptr(images), K.ptr(out), table, B, H, W, K.ptr(ws), nb),
+                   "clipmi_affine_u8")
+    return out
+
+
+def rotation_matrix(angle, w, h, center=None):
+    """PIL Image.rotate's matrix for a w x h image (PIL/Image.py): counter-clockwise by ``angle`` degrees about
+    ``center`` (default (w / 2, h / 2)), as output pixel -> source coordinate."""
+    angle = angle % 360.0
+    cx, cy = (w / 2.0, h / 2.0) if center is None else (float(center[0]), float(center[1]))
+    t = -math.radians(angle)
+    m = [round(math.cos(t), 15), round(math.sin(t), 15), 0.0, round(-math.sin(t), 15), round(math.cos(t), 15), 0.0]
+    x, y = -cx, -cy
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def affine_matrix(angle=0.0, translate=(0, 0), scale=1.0, shear=(0.0, 0.0), w=1, h=1, center=None):
+    """torchvision's published _get_inverse_affine_matrix as F.affine calls it for a w x h PIL image: the inverse of
+    T * C * R(angle) * Shear(shear) * Scale(scale) * C^-1 with C the translation to ``center`` (default (w * 0.5,
+    h * 0.5)); angle and shear (x, y) in degrees, translate (tx, ty) in pixels."""
+    cx, cy = (w * 0.5, h * 0.5) if center is None else (float(center[0]), float(center[1]))
+    tx, ty = translate
+    rot, sx, sy = math.radians(angle), math.radians(shear[0]), math.radians(shear[1])
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [v / scale for v in (d, -b, 0.0, -c, a, 0.0)]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
 
 
 def _uniform(generator, lo, hi):
@@ -333,25 +485,145 @@ class ColorJitter:
         return items
 
 
+def _number_range(who, name, value, n=(2,)):
+    """torchvision's _setup_angle: a number d is (-d, d) with d >= 0; else a sequence of one of the lengths n."""
+    if isinstance(value, (int, float)) and not isinstance(value, bool):
+        if not math.isfinite(value) or value < 0:
+            raise ValueError(f"{who}: a single {name} must be a finite number >= 0, got {value}")
+        return (-float(value), float(value))
+    if not isinstance(value, (tuple, list)) or len(value) not in n or \
+            not all(isinstance(v, (int, float)) and math.isfinite(v) for v in value):
+        raise ValueError(f"{who}: {name} must be a number or a sequence of {' or '.join(map(str, n))} numbers, got {value!r}")
+    return tuple(float(v) for v in value)
+
+
+def _check_p(who, p):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"{who}: p must be in [0, 1], got {p}")
+    return p
+
+
+def _check_center(who, center):
+    if center is None:
+        return None
+    if not isinstance(center, (tuple, list)) or len(center) != 2:
+        raise ValueError(f"{who}: center must be an (x, y) pair, got {center!r}")
+    return (float(center[0]), float(center[1]))
+
+
+class RandomAffine:
+    """torchvision's RandomAffine on PIL images as a sampler of per-image AffineItem records.  ``degrees``: d for
+    angles in (-d, d), or (lo, hi); ``translate``: (fx, fy) fractions in [0, 1] of the width and the height;
+    ``scale``: a positive (lo, hi); ``shear``: s for an x shear in (-s, s), (lo, hi), or (xlo, xhi, ylo, yhi), in
+    degrees; ``interpolation``: "nearest" | "bilinear"; ``fill``: an int or an (r, g, b) triple; ``center``: the
+    image centre when None; ``p``: the probability that an image is transformed at all (RandomApply).
+    ``sample(B, size, generator)`` with size = (w, h), or a number for a square, follows RandomAffine.get_params per
+    image: the angle, then tx and ty (int(round(U(-max_d, max_d))), max_dx = translate[0] * w), then the scale, then
+    shear_x and, for a 4-tuple, shear_y.  With p < 1 one uniform is drawn first and an image that is skipped gets the
+    identity item and no further draws; with p == 1 no coin is drawn.  expand is not offered."""
+
+    def __init__(self, degrees, translate=None, scale=None, shear=None, interpolation="nearest", fill=0, center=None,
+                 p=1.0):
+        who = type(self).__name__
+        self.degrees = _number_range(who, "degrees", degrees)
+        if translate is not None:
+            if not isinstance(translate, (tuple, list)) or len(translate) != 2 or \
+                    not all(isinstance(t, (int, float)) and 0.0 <= t <= 1.0 for t in translate):
+                raise ValueError(f"{who}: translate must be a pair of fractions in [0, 1], got {translate!r}")
+            translate = (float(translate[0]), float(translate[1]))
+        self.translate = translate
+        if scale is not None:
+            if not isinstance(scale, (tuple, list)) or len(scale) != 2 or \
+                    not all(isinstance(v, (int, float)) and math.isfinite(v) and v > 0 for v in scale):
+                raise ValueError(f"{who}: scale must be a pair of positive numbers, got {scale!r}")
+            scale = (float(scale[0]), float(scale[1]))
+        self.scale = scale
+        self.shear = None if shear is None else _number_range(who, "shear", shear, (2, 4))
+        self.filter = _filter_code(who, interpolation)
+        self.interpolation = interpolation
+        self.fill = _fill_code(who, fill)
+        self.center = _check_center(who, center)
+        self.p = _check_p(who, p)
+
+    def params(self, w, h, generator=None):
+        """One get_params draw: (angle, (tx, ty), scale, (shear_x, shear_y))."""
+        angle = _uniform(generator, self.degrees[0], self.degrees[1])
+        tx = ty = 0
+        if self.translate is not None:
+            max_dx, max_dy = float(self.translate[0] * w), float(self.translate[1] * h)
+            tx = int(round(_uniform(generator, -max_dx, max_dx)))
+            ty = int(round(_uniform(generator, -max_dy, max_dy)))
+        scale = 1.0 if self.scale is None else _uniform(generator, self.scale[0], self.scale[1])
+        shear_x = shear_y = 0.0
+        if self.shear is not None:
+            shear_x = _uniform(generator, self.shear[0], self.shear[1])
+            if len(self.shear) == 4:
+                shear_y = _uniform(generator, self.shear[2], self.shear[3])
+        return angle, (tx, ty), scale, (shear_x, shear_y)
+
+    def matrix(self, w, h, generator=None):
+        angle, translate, scale, shear = self.params(w, h, generator)
+        return affine_matrix(angle, translate, scale, shear, w, h, self.center)
+
+    def sample(self, B, size, generator=None):
+        w, h = (size, size) if isinstance(size, (int, float)) else size
+        w, h = int(w), int(h)
+        items = []
+        for _ in range(int(B)):
+            if self.p < 1.0 and not float(torch.rand((), generator=generator)) < self.p:
+                m = AFFINE_IDENTITY
+            else:
+                m = self.matrix(w, h, generator)
+            it = AffineItem.of(m, self.interpolation)
+            it.fill = self.fill
+            items.append(it)
+        return items
+
+
+class RandomRotation(RandomAffine):
+    """torchvision's RandomRotation on PIL images (Image.rotate without expand) as a sampler of per-image AffineItem
+    records: one uniform angle per image from ``degrees`` (d for (-d, d), or (lo, hi)), counter-clockwise, through
+    ``rotation_matrix``.  ``p`` as in RandomAffine."""
+
+    def __init__(self, degrees, interpolation="nearest", fill=0, center=None, p=1.0):
+        super().__init__(degrees, interpolation=interpolation, fill=fill, center=center, p=p)
+
+    def matrix(self, w, h, generator=None):
+        return rotation_matrix(_uniform(generator, self.degrees[0], self.degrees[1]), w, h, self.center)
+
+
 class TrainAugment:
     """ImageBatch -> ImageBatch with a random-resized-crop box and a flip bit per image, ``mode="square"``, and,
-    with ``color`` (a ColorJitter), a colour record per image.  Its own generator (``seed``) makes a run
-    reproducible; the colour records are drawn after the boxes and the flips, so a seed gives the same boxes and
-    flips with or without colour."""
+    with ``color`` (a ColorJitter), a colour record per image, and, with ``affine`` (a RandomAffine or a
+    RandomRotation) and the output size ``image_size``, an affine record per image.  Its own generator (``seed``)
+    makes a run reproducible; the colour records are drawn after the boxes and the flips and the affine records
+    last, so a seed gives the same boxes, flips and colour records with or without them."""
 
-    def __init__(self, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0, color=None):
+    def __init__(self, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0, color=None, affine=None,
+                 image_size=None):
         self.scale, self.ratio, self.flip_p = tuple(scale), tuple(ratio), float(flip_p)
         self.generator = torch.Generator(device="cpu").manual_seed(int(seed))
         if color is not None and not isinstance(color, ColorJitter):
             raise ValueError("TrainAugment: color must be a ColorJitter or None")
         self.color = color
+        if affine is not None and not isinstance(affine, RandomAffine):
+            raise ValueError("TrainAugment: affine must be a RandomAffine, a RandomRotation or None")
+        self.affine = affine
+        self.image_size = None if image_size is None else int(image_size)
 
-    def __call__(self, batch):
+    def __call__(self, batch, image_size=None):
         boxes = random_resized_crop_boxes(batch.sizes, self.scale, self.ratio, self.generator)
         flips = random_flips(len(batch), self.flip_p, self.generator)
         out = batch.with_boxes(boxes).with_flips(flips).with_mode("square")
         if self.color is not None:
             out = out.with_color(self.color.sample(len(batch), self.generator))
+        if self.affine is not None:
+            size = self.image_size if image_size is None else int(image_size)
+            if size is None:
+                raise ValueError("TrainAugment: affine records need the output size (image_size here or in the call): "
+                                 "the matrices turn about the output's centre and translate by fractions of it")
+            out = out.with_affine(self.affine.sample(len(batch), size, self.generator))
         return out
 
 

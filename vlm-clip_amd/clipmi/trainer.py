@@ -18,7 +18,7 @@ from . import _lib
 from . import comm as CM
 from . import kernels as K
 from . import towers as T
-from .images import ImageBatch
+from .images import ImageBatch, TrainAugment
 from .losses import batch_keys
 
 
@@ -303,7 +303,11 @@ class CLIPAdapterTrainer:
         device = self.model.clip.arena.device
         batch = _to_device(batch, device, True)
         if self.augment is not None and isinstance(batch.get("pixel_values"), ImageBatch):
-            batch["pixel_values"] = self.augment(batch["pixel_values"])
+            if isinstance(self.augment, TrainAugment):  # its affine records turn about the model's input centre
+                batch["pixel_values"] = self.augment(batch["pixel_values"],
+                                                     image_size=self.model.config.vision_config.image_size)
+            else:
+                batch["pixel_values"] = self.augment(batch["pixel_values"])
         outputs = self.model(input_ids=batch.get("input_ids"), attention_mask=batch.get("attention_mask"),
                              pixel_values=batch.get("pixel_values"), return_loss=True,
                              **self._loss_kwargs(batch, device))
