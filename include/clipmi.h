@@ -41,7 +41,8 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
  * 9: clipmi_color_u8 (colour augmentation of the input step)
  * 10: clipmi_gemm_plan
  * 11: clipmi_sigmoid_pairs, clipmi_sigmoid_reduce (pairwise sigmoid contrastive head)
- * 12: clipmi_affine_u8 (affine / rotation augmentation of the input step) */
+ * 12: clipmi_affine_u8 (affine / rotation augmentation of the input step)
+ * 13: clipmi_enhance_u8 (posterize, solarize, autocontrast, equalize, sharpness: the policy ops of the input step) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -364,6 +365,43 @@ typedef struct clipmi_affine_item {
 int64_t clipmi_affine_u8_ws(const clipmi_affine_item* items, int B, int H, int W);
 int clipmi_affine_u8(void* stream, const uint8_t* src, uint8_t* dst, const clipmi_affine_item* items, int B, int H,
                      int W, void* ws, int64_t ws_bytes);
+/* Policy ops without an affine or a colour kernel (csrc/enhance.hip; clipmi_version() >= 13): PIL's ImageOps.posterize /
+ * solarize / autocontrast / equalize and ImageEnhance.Sharpness bit for bit: src uint8 [B, H, W, 3] -> dst of the same
+ * shape, image b through items[b]'s one op.  With clipmi_affine_u8 and clipmi_color_u8 these are the fourteen ops of
+ * torchvision's RandAugment and TrivialAugmentWide on PIL images (clipmi/images.py apply_policy_u8 runs a per-image
+ * sequence of them).  h_c is channel c's 256-bin histogram over the image; the LUTs are per channel.
+ *   0 none:         dst = src
+ *   1 posterize:    value = bits, an integer in 1..8; i & ~(2^(8 - bits) - 1)               (ImageOps.posterize)
+ *   2 solarize:     value = threshold; (float)i < value ? i : 255 - i                       (ImageOps.solarize)
+ *   3 autocontrast: lo, hi = the first, last non-empty bin; hi <= lo: the identity; else, in double, each operation
+ *                   rounded on its own (no fma): scale = 255.0 / (hi - lo), offset = -lo * scale,
+ *                   lut[i] = clamp((int)(i * scale + offset), 0, 255), truncated toward zero: a channel that holds
+ *                   only 0 and 200 maps 200 to 254                                          (ImageOps.autocontrast, cutoff 0)
+ *   4 equalize:     fewer than two non-empty bins: the identity; step = (sum h - the last non-empty bin) / 255
+ *                   (integers); 0: the identity; else n = step / 2 and for i = 0..255: lut[i] = min(n / step, 255),
+ *                   n += h[i] (Image.point stores a list LUT's entries clipped to a byte)   (ImageOps.equalize)
+ *   5 sharpness:    value = factor >= 0.  d = ImageFilter.SMOOTH of the image: k = (1,1,1,1,5,1,1,1,1) / 13 as float32
+ *                   quotients; a float32 accumulator ss = 0.5 takes the three rows one after the other,
+ *                   ss += (k0 left + k1 mid) + k2 right, every product and sum a float32 operation of its own; d = 0
+ *                   where ss <= 0, 255 where ss >= 255, else trunc(ss); the one-pixel frame of the image is the
+ *                   source's, so an image with H < 3 or W < 3 is left whole.  dst = blend(d, src, value), the blend of
+ *                   clipmi_color_u8                                                         (ImageEnhance.Sharpness)
+ * `items` is host memory: every item is validated before any launch (an unknown op, a non-finite value, posterize bits
+ * that are no integer in 1..8, a negative sharpness factor return CLIPMI_ERR_INVALID naming the item; so do B < 0,
+ * B > 65535, H or W < 1, H * W > 2^24 -- the range of the 32-bit bins and sums -- null pointers and src and dst that
+ * overlap) and the records are uploaded into the workspace on the stream; the kernels read that copy and src only.  At
+ * most three launches whatever B is: the histograms of the autocontrast and equalize images (integer atomics into a
+ * [B][768] table zeroed by a memset node: bitwise reproducible), their LUTs (one block per image), then every pixel
+ * through its image's op; one launch when no item needs a histogram.  No host synchronisation.  B == 0 returns.
+ * clipmi_enhance_u8_ws returns the workspace bytes (a negative status on invalid items); the workspace must be 16-byte
+ * aligned. */
+typedef struct clipmi_enhance_item {
+  int32_t op;      /* 0 none, 1 posterize, 2 solarize, 3 autocontrast, 4 equalize, 5 sharpness */
+  float   value;   /* posterize: bits; solarize: threshold; sharpness: factor; else ignored (finite) */
+} clipmi_enhance_item;
+int64_t clipmi_enhance_u8_ws(const clipmi_enhance_item* items, int B, int H, int W);
+int clipmi_enhance_u8(void* stream, const uint8_t* src, uint8_t* dst, const clipmi_enhance_item* items, int B, int H,
+                      int W, void* ws, int64_t ws_bytes);
 /* pooled token per row: mode 0 first token (model_m.py:102), 1 first EOS (0 when the row has none), 2 argmax id,
  * the first of tied maxima ([HF] :561-581).  gather: out[b] = src[b*S + idx[b]]; scatter: dst[b*S + idx[b]] (+)=
  * src[b], the other rows of dst untouched; idx NULL: token 0.  B = 0 is a no-op. */

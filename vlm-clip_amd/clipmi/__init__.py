@@ -31,7 +31,8 @@ def __getattr__(name):
 
 _IMAGES = ("ImageBatch", "preprocess", "random_resized_crop_boxes", "random_flips", "TrainAugment", "collate",
            "ColorItem", "ColorJitter", "color_jitter_u8", "AffineItem", "affine_u8", "rotation_matrix", "affine_matrix",
-           "RandomAffine", "RandomRotation")
+           "RandomAffine", "RandomRotation", "EnhanceItem", "enhance_u8", "apply_policy_u8", "RandAugment",
+           "TrivialAugmentWide")
 _EVALUATION = ("RankResult", "target_ranks", "TopK", "topk", "recall_at_k", "rank_summary", "evaluate_retrieval",
                "ClassificationMeter", "ClassificationResult", "classification_report", "accuracy", "evaluate_model",
                "evaluate_enhanced_model", "GroupRankResult", "group_ranks", "topk_relevance", "precision_at_k",

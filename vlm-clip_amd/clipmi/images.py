@@ -30,7 +30,15 @@ launch whatever B is), which is what torchvision's RandomAffine / RandomRotation
 ``RandomAffine`` / ``RandomRotation`` sample per-image ``AffineItem`` records as their ``get_params`` do.  An
 ``ImageBatch`` that carries them (``with_affine``) gets them applied by ``preprocess`` after the resize, the window
 and the flip and in front of the colour records: Compose([RandomResizedCrop, RandomHorizontalFlip, RandomAffine,
-ColorJitter])."""
+ColorJitter]).
+
+Policies: ``enhance_u8`` is PIL's ImageOps.posterize / solarize / autocontrast / equalize and ImageEnhance.Sharpness
+bit for bit, each image with its own op (include/clipmi.h clipmi_enhance_u8: at most three launches whatever B is).
+``apply_policy_u8`` runs a per-image sequence of torchvision's fourteen policy ops over the three kernel families,
+stage by stage, so its launches are bounded per stage and not per image; ``RandAugment`` and ``TrivialAugmentWide``
+sample such sequences as the published torchvision classes do.  An ``ImageBatch`` that carries them (``with_policy``)
+gets them applied by ``preprocess`` after the resize, the window and the flip and in front of the affine and the
+colour records."""
 from __future__ import annotations
 
 import ctypes
@@ -131,6 +139,25 @@ class AffineItem(ctypes.Structure):
 
 
 AFFINE_IDENTITY = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0]
+ENHANCE_OPS = {"none": 0, "posterize": 1, "solarize": 2, "autocontrast": 3, "equalize": 4, "sharpness": 5}
+
+
+class EnhanceItem(ctypes.Structure):
+    """include/clipmi.h clipmi_enhance_item.  ``EnhanceItem.of`` builds one from an op name."""
+    _fields_ = [("op", ctypes.c_int32), ("value", ctypes.c_float)]
+
+    @classmethod
+    def of(cls, name, value=0):
+        """name in ENHANCE_OPS; value: posterize's bits (an integer in 1..8), solarize's threshold, sharpness's
+        factor (1 leaves the image as it is); "none", "autocontrast" and "equalize" take none."""
+        if name not in ENHANCE_OPS:
+            raise ValueError(f"EnhanceItem.of: op must be one of {sorted(ENHANCE_OPS)}, got {name!r}")
+        return cls(ENHANCE_OPS[name], float(value))
+
+    @property
+    def name(self):
+        return {v: k for k, v in ENHANCE_OPS.items()}[self.op]
+
 
 _lib.declare("clipmi_resize_crop_u8_ws", [ctypes.POINTER(ImageItem), ctypes.c_int, ctypes.c_int, ctypes.c_int],
              ctypes.c_int64)
@@ -145,6 +172,10 @@ _lib.declare("clipmi_affine_u8_ws", [ctypes.POINTER(AffineItem), ctypes.c_int, c
              ctypes.c_int64)
 _lib.declare("clipmi_affine_u8", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(AffineItem),
                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64])
+_lib.declare("clipmi_enhance_u8_ws", [ctypes.POINTER(EnhanceItem), ctypes.c_int, ctypes.c_int, ctypes.c_int],
+             ctypes.c_int64)
+_lib.declare("clipmi_enhance_u8", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(EnhanceItem),
+                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64])
 
 
 class ImageBatch:
@@ -154,9 +185,13 @@ class ImageBatch:
     ``sizes``: [(h, w)]; ``offsets``: byte offset of each image; ``boxes``: [(x0, y0, cw, ch)] (default:
     the whole image); ``flips``: [0 | 1] (default 0); ``mode``: "processor" | "square"; ``color``: one ColorItem
     per image, applied to ``preprocess``'s output (default None: no colour pass); ``affine``: one AffineItem per
-    image, applied after the resize, the window and the flip and in front of ``color`` (default None: no such pass)."""
+    image, applied after the resize, the window and the flip and in front of ``color`` (default None: no such pass);
+    ``policy``: (programs, interpolation, fill) as ``with_policy`` stores them, one policy program per image, run
+    through ``apply_policy_u8`` after the resize, the window and the flip and in front of ``affine`` and ``color``
+    (default None: no such pass)."""
 
-    def __init__(self, data, sizes, offsets, boxes=None, flips=None, mode="processor", color=None, affine=None):
+    def __init__(self, data, sizes, offsets, boxes=None, flips=None, mode="processor", color=None, affine=None,
+                 policy=None):
         if mode not in MODES:
             raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
         self.data = data
@@ -173,6 +208,12 @@ class ImageBatch:
         if self.affine is not None and (len(self.affine) != n or
                                         not all(isinstance(it, AffineItem) for it in self.affine)):
             raise ValueError("ImageBatch: affine must have one AffineItem per image")
+        self.policy = None
+        if policy is not None:
+            programs, interpolation, fill = policy
+            _filter_code("ImageBatch", interpolation)
+            _fill_code("ImageBatch", 0 if fill is None else fill)
+            self.policy = (_check_programs("ImageBatch", programs, n), interpolation, fill)
         if not (len(self.offsets) == len(self.boxes) == len(self.flips) == n):
             raise ValueError("ImageBatch: sizes, offsets, boxes and flips must have one entry per image")
         if any(len(b) != 4 for b in self.boxes):
@@ -201,7 +242,7 @@ class ImageBatch:
 
     def _like(self, **kw):
         a = dict(data=self.data, sizes=self.sizes, offsets=self.offsets, boxes=self.boxes, flips=self.flips,
-                 mode=self.mode, color=self.color, affine=self.affine)
+                 mode=self.mode, color=self.color, affine=self.affine, policy=self.policy)
         a.update(kw)
         return ImageBatch(**a)
 
@@ -230,6 +271,11 @@ class ImageBatch:
     def with_affine(self, items):
         return self._like(affine=items)
 
+    def with_policy(self, programs, interpolation="nearest", fill=0):
+        """programs[b]: image b's [(op name, magnitude)] (``apply_policy_u8``; RandAugment / TrivialAugmentWide
+        ``sample``); None removes them."""
+        return self._like(policy=None if programs is None else (programs, interpolation, fill))
+
     def items(self):
         """The clipmi_image_item table (host)."""
         arr = (ImageItem * max(len(self), 1))()
@@ -243,7 +289,9 @@ def preprocess(batch, image_size, mode=None, out=None):
     batch's own when None.  out: a contiguous uint8 view of B*S*S*3 elements to write into.  A batch with affine
     records (``with_affine``) has the resize write a scratch [B, S, S, 3] and clipmi_affine_u8 write the output (one
     more launch); a batch with colour records (``with_color``) then gets them applied to the output in place
-    (clipmi_color_u8, two more launches)."""
+    (clipmi_color_u8, two more launches).  A batch with policy programs (``with_policy``) has them run by
+    ``apply_policy_u8`` on the resize's output, in front of the affine and the colour records: where
+    Compose([RandomResizedCrop, RandomHorizontalFlip, RandAugment, ...]) puts them."""
     mode = batch.mode if mode is None else mode
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
@@ -261,10 +309,15 @@ def preprocess(batch, image_size, mode=None, out=None):
         elif out.dtype != torch.uint8 or out.numel() != B * S * S * 3 or not out.is_contiguous():
             raise ValueError("preprocess: out must be a contiguous uint8 view of B*S*S*3 elements")
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=batch.data.device)
-        resized = out if batch.affine is None else torch.empty(B, S, S, 3, dtype=torch.uint8, device=batch.data.device)
+        out = out.view(B, S, S, 3)
+        # every out-of-place pass reads a scratch tensor; the last one writes the output
+        passes = (batch.policy is not None) + (batch.affine is not None)
+        resized = out if passes == 0 else torch.empty_like(out)
         _lib.check(L.clipmi_resize_crop_u8(K.stream(), K.ptr(batch.data), batch.data.numel(), items, B, K.ptr(resized),
                                            S, MODES[mode], K.ptr(ws), nb), "clipmi_resize_crop_u8")
-    out = out.view(B, S, S, 3)
+    if batch.policy is not None:
+        programs, interpolation, fill = batch.policy
+        resized = apply_policy_u8(resized, programs, interpolation, fill, out=out if passes == 1 else None)
     if batch.affine is not None:
         affine_u8(resized, batch.affine, out=out)
     if batch.color is not None:
@@ -328,12 +381,7 @@ def affine_u8(images, items, out=None):
     if n != B:
         raise ValueError(f"affine_u8: {n} records for {B} images")
     if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(images.shape)
-                or not out.is_contiguous() or out.device != images.device):
-            raise ValueError("affine_u8: out must be a contiguous uint8 tensor of images' shape on images' device")
-        lo, hi, nbytes = images.data_ptr(), out.data_ptr(), images.numel()
-        if nbytes and lo < hi + nbytes and hi < lo + nbytes:
-            raise ValueError("affine_u8: out must not alias images (every output pixel gathers from the source image)")
+        _check_out("affine_u8", images, out, "every output pixel gathers from the source image")
     L = _lib.lib()
     nb = int(L.clipmi_affine_u8_ws(table, B, max(H, 1) if B == 0 else H, max(W, 1) if B == 0 else W))
     if nb < 0:
@@ -346,6 +394,180 @@ def affine_u8(images, items, out=None):
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=images.device)
         _lib.check(L.clipmi_affine_u8(K.stream(), K.ptr(images), K.ptr(out), table, B, H, W, K.ptr(ws), nb),
                    "clipmi_affine_u8")
+    return out
+
+
+def _check_out(who, images, out, why):
+    """``out`` as an out-of-place call takes it: images' shape, dtype and device, contiguous, no byte shared."""
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(images.shape)
+            or not out.is_contiguous() or out.device != images.device):
+        raise ValueError(f"{who}: out must be a contiguous uint8 tensor of images' shape on images' device")
+    lo, hi, nbytes = images.data_ptr(), out.data_ptr(), images.numel()
+    if nbytes and lo < hi + nbytes and hi < lo + nbytes:
+        raise ValueError(f"{who}: out must not alias images ({why})")
+
+
+def enhance_u8(images, items, out=None):
+    """uint8 [B, H, W, 3] on the GPU through clipmi_enhance_u8: image b through items[b]'s op (EnhanceItem.of:
+    posterize, solarize, autocontrast, equalize, sharpness as PIL's ImageOps / ImageEnhance do them, or none).
+    Returns a new tensor, or ``out`` (uint8 [B, H, W, 3], contiguous, on the same device, no byte shared with
+    ``images``).  ``images`` is left as it is."""
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("enhance_u8: images must be uint8 [B, H, W, 3]")
+    if not images.is_cuda:
+        raise ValueError("enhance_u8 needs the images on the GPU; there is no CPU fallback")
+    if not images.is_contiguous():
+        raise ValueError("enhance_u8: images must be contiguous")
+    B, H, W = (int(v) for v in images.shape[:3])
+    n = len(items)
+    if not all(isinstance(it, EnhanceItem) for it in items):
+        raise ValueError("enhance records must be EnhanceItem (EnhanceItem.of)")
+    if n != B:
+        raise ValueError(f"enhance_u8: {n} records for {B} images")
+    table = (EnhanceItem * max(n, 1))(*items)
+    if out is not None:
+        _check_out("enhance_u8", images, out, "sharpness reads every pixel's neighbours")
+    L = _lib.lib()
+    nb = int(L.clipmi_enhance_u8_ws(table, B, max(H, 1) if B == 0 else H, max(W, 1) if B == 0 else W))
+    if nb < 0:
+        _lib.check(nb, "clipmi_enhance_u8_ws")
+    with torch.cuda.device(images.device):
+        if out is None:
+            out = torch.empty_like(images)
+        if B == 0:
+            return out
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=images.device)
+        _lib.check(L.clipmi_enhance_u8(K.stream(), K.ptr(images), K.ptr(out), table, B, H, W, K.ptr(ws), nb),
+                   "clipmi_enhance_u8")
+    return out
+
+
+# torchvision's policy ops (autoaugment._apply_op), in the order of RandAugment's and TrivialAugmentWide's op table
+POLICY_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+              "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
+_POLICY_AFFINE = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
+_POLICY_COLOR = {"Brightness": "brightness", "Color": "saturation", "Contrast": "contrast"}
+_POLICY_ENHANCE = {"Sharpness": "sharpness", "Posterize": "posterize", "Solarize": "solarize",
+                   "AutoContrast": "autocontrast", "Equalize": "equalize"}
+
+
+def _check_programs(who, programs, n):
+    """programs as [[(op name, float magnitude)]], one list per image."""
+    programs = [list(p) for p in programs]
+    if len(programs) != n:
+        raise ValueError(f"{who}: {len(programs)} programs for {n} images")
+    out = []
+    for b, prog in enumerate(programs):
+        ops = []
+        for op in prog:
+            if not isinstance(op, (tuple, list)) or len(op) != 2 or op[0] not in POLICY_OPS:
+                raise ValueError(f"{who}: program {b}: an op is (name, magnitude) with name in {list(POLICY_OPS)}, "
+                                 f"got {op!r}")
+            ops.append((op[0], float(op[1])))
+        out.append(ops)
+    return out
+
+
+def policy_matrix(name, m, w, h):
+    """The matrix autoaugment._apply_op hands to PIL for a geometric op of magnitude m on a w x h image."""
+    if name == "ShearX":
+        return affine_matrix(0.0, (0, 0), 1.0, (math.degrees(math.atan(m)), 0.0), w, h, center=(0, 0))
+    if name == "ShearY":
+        return affine_matrix(0.0, (0, 0), 1.0, (0.0, math.degrees(math.atan(m))), w, h, center=(0, 0))
+    if name == "TranslateX":
+        return affine_matrix(0.0, (int(m), 0), 1.0, (0.0, 0.0), w, h)
+    if name == "TranslateY":
+        return affine_matrix(0.0, (0, int(m)), 1.0, (0.0, 0.0), w, h)
+    if name == "Rotate":
+        return rotation_matrix(m, w, h)
+    raise ValueError(f"policy_matrix: {name!r} is not one of {list(_POLICY_AFFINE)}")
+
+
+def policy_calls(programs, w, h, interpolation="nearest", fill=0):
+    """The calls ``apply_policy_u8`` makes for these programs on w x h images: [(kind, items)] with kind in
+    "affine" | "enhance" | "color" and one record per image.  Stage k holds every image's k-th op (the identity for
+    a shorter program); a stage is at most one call of each kind, in that order, and a kind no image of the stage
+    uses is left out."""
+    return _policy_calls(_check_programs("apply_policy_u8", programs, len(programs)), w, h, interpolation, fill)
+
+
+def _policy_calls(programs, w, h, interpolation, fill):
+    """policy_calls on checked programs.  The records of the images a call leaves alone are one shared instance per
+    kind: a call copies its records into a table."""
+    filt, fc = _filter_code("apply_policy_u8", interpolation), _fill_code("apply_policy_u8", 0 if fill is None else fill)
+    same = {"affine": AffineItem.of(AFFINE_IDENTITY), "enhance": EnhanceItem.of("none"), "color": ColorItem.of([])}
+
+    def record(kind, name, m):
+        if kind == "affine":
+            return AffineItem((ctypes.c_double * 6)(*policy_matrix(name, m, w, h)), filt, fc)
+        if kind == "color":
+            return ColorItem.of([(_POLICY_COLOR[name], 1.0 + m)])
+        return EnhanceItem.of(_POLICY_ENHANCE[name], {"Sharpness": 1.0 + m, "Posterize": int(m), "Solarize": m}.get(name, 0))
+
+    kind_of = dict([(n, "affine") for n in _POLICY_AFFINE] + [(n, "enhance") for n in _POLICY_ENHANCE] +
+                   [(n, "color") for n in _POLICY_COLOR])
+    calls = []
+    for k in range(max((len(p) for p in programs), default=0)):
+        ops = [p[k] if k < len(p) else ("Identity", 0.0) for p in programs]
+        kinds = [kind_of.get(name) for name, _ in ops]
+        for kind in ("affine", "enhance", "color"):
+            if kind in kinds:
+                calls.append((kind, [record(kind, name, m) if kd == kind else same[kind]
+                                     for kd, (name, m) in zip(kinds, ops)]))
+    return calls
+
+
+def apply_policy_u8(images, programs, interpolation="nearest", fill=0, out=None):
+    """uint8 [B, H, W, 3] on the GPU through per-image sequences of torchvision's policy ops, bit for bit what
+    autoaugment._apply_op does to PIL images.  programs[b]: [(op name, magnitude)] for image b in the order the ops
+    run, names in POLICY_OPS, the magnitude carrying its sign: ShearX / ShearY shear by atan(m) about the corner (0, 0),
+    TranslateX / TranslateY shift by int(m) pixels, Rotate turns by m degrees; Brightness / Color / Contrast / Sharpness
+    take the factor 1 + m; Posterize keeps int(m) bits; Solarize inverts bytes at or above m (compared as float32);
+    Identity, AutoContrast and Equalize take none.  The geometric ops use ``interpolation`` ("nearest" | "bilinear")
+    and ``fill`` (None: black).
+
+    Execution is by stage (``policy_calls``): per stage at most one affine_u8, one enhance_u8 and one color_jitter_u8
+    call over the whole batch, so the launches are bounded per stage, not per image: at most 2 + 3 + 2.  The
+    out-of-place calls go back and forth between two scratch tensors and the last write lands in the result.
+    Returns a new tensor, or ``out`` (no byte shared with ``images``); ``images`` is left as it is."""
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("apply_policy_u8: images must be uint8 [B, H, W, 3]")
+    if not images.is_cuda:
+        raise ValueError("apply_policy_u8 needs the images on the GPU; there is no CPU fallback")
+    if not images.is_contiguous():
+        raise ValueError("apply_policy_u8: images must be contiguous")
+    B, H, W = (int(v) for v in images.shape[:3])
+    calls = _policy_calls(_check_programs("apply_policy_u8", programs, B), W, H, interpolation, fill)
+    if out is not None:
+        _check_out("apply_policy_u8", images, out, "the first op reads the source while the result is written")
+    with torch.cuda.device(images.device):
+        if out is None:
+            out = torch.empty_like(images)
+        moves = sum(kind != "color" for kind, _ in calls)  # out-of-place calls still to come
+        scratch = []
+        cur = images
+
+        def target():
+            """Where the next write goes: ``out`` when no out-of-place call follows, else a scratch tensor that is
+            not the one being read."""
+            if moves == 0:
+                return out
+            for t in scratch:
+                if t is not cur:
+                    return t
+            scratch.append(torch.empty_like(images))
+            return scratch[-1]
+
+        for kind, items in calls:
+            if kind == "color":
+                if cur is images:  # the in-place call must not touch the source
+                    cur = target().copy_(images)
+                color_jitter_u8(cur, items)
+            else:
+                moves -= 1
+                cur = (affine_u8 if kind == "affine" else enhance_u8)(cur, items, out=target())
+        if cur is not out:  # nothing ran
+            out.copy_(images)
     return out
 
 
@@ -593,15 +815,107 @@ class RandomRotation(RandomAffine):
         return rotation_matrix(_uniform(generator, self.degrees[0], self.degrees[1]), w, h, self.center)
 
 
+class _PolicySampler:
+    """What RandAugment and TrivialAugmentWide share: the op table of the published torchvision classes (POLICY_OPS in
+    its order; per op a float32 ``torch.linspace`` / ``arange`` table of magnitudes, or none, and whether the sign is
+    drawn) and the draws, all from the CPU generator given: per op ``randint(14)`` for the op; for TrivialAugmentWide
+    only, and only for an op with a table, ``randint(bins)`` for the magnitude; only for a signed op ``randint(2)``,
+    where 1 negates.  A magnitude is ``float(table[idx])``.  torchvision itself is not a dependency and was not at
+    hand when this was written: the samplers are pinned to the published definition through hand-derived values
+    (tests/test_cpu_enhance.py), not to torchvision's own draws."""
+
+    def __init__(self, num_magnitude_bins, interpolation, fill):
+        who = type(self).__name__
+        self.num_magnitude_bins = int(num_magnitude_bins)
+        if self.num_magnitude_bins < 2:
+            raise ValueError(f"{who}: num_magnitude_bins must be >= 2, got {num_magnitude_bins}")
+        _filter_code(who, interpolation)
+        _fill_code(who, 0 if fill is None else fill)
+        self.interpolation, self.fill = interpolation, fill
+
+    def space(self, w, h):
+        """{op name: (table or None, signed)} for a w x h image, in POLICY_OPS' order."""
+        raise NotImplementedError
+
+    def _space(self, w, h, shear, translate_x, translate_y, rotate, enhance, posterize_steps):
+        bins = self.num_magnitude_bins
+        lin = lambda hi: torch.linspace(0.0, hi, bins)  # noqa: E731
+        posterize = 8 - (torch.arange(bins) / ((bins - 1) / posterize_steps)).round().int()
+        return {"Identity": (None, False), "ShearX": (lin(shear), True), "ShearY": (lin(shear), True),
+                "TranslateX": (lin(translate_x), True), "TranslateY": (lin(translate_y), True),
+                "Rotate": (lin(rotate), True), "Brightness": (lin(enhance), True), "Color": (lin(enhance), True),
+                "Contrast": (lin(enhance), True), "Sharpness": (lin(enhance), True), "Posterize": (posterize, False),
+                "Solarize": (torch.linspace(255.0, 0.0, bins), False), "AutoContrast": (None, False),
+                "Equalize": (None, False)}
+
+    def _index(self, table, generator):
+        raise NotImplementedError
+
+    def _draw(self, space, generator):
+        name = POLICY_OPS[int(torch.randint(len(POLICY_OPS), (1,), generator=generator))]
+        table, signed = space[name]
+        magnitude = 0.0 if table is None else float(table[self._index(table, generator)])
+        if signed and int(torch.randint(2, (1,), generator=generator)):
+            magnitude *= -1.0
+        return name, magnitude
+
+    def sample(self, B, size, generator=None):
+        """B programs ([(op name, magnitude)]) for images of ``size`` = (w, h), or a number for a square."""
+        w, h = (size, size) if isinstance(size, (int, float)) else size
+        space = self.space(int(w), int(h))
+        assert tuple(space) == POLICY_OPS
+        return [[self._draw(space, generator) for _ in range(self.num_ops)] for _ in range(int(B))]
+
+
+class RandAugment(_PolicySampler):
+    """torchvision's RandAugment on PIL images as a sampler of per-image policy programs for ``apply_policy_u8`` /
+    ``ImageBatch.with_policy``: ``num_ops`` ops per image, each uniform over the fourteen POLICY_OPS, every magnitude
+    the table entry at ``magnitude`` (of ``num_magnitude_bins``): shears to 0.3, translations to 150 / 331 of the
+    width or height, rotations to 30 degrees, enhancement factors 1 +- up to 0.9, posterize 8 down to 4 bits,
+    solarize thresholds 255 down to 0.  Draw order and tables: see _PolicySampler."""
+
+    def __init__(self, num_ops=2, magnitude=9, num_magnitude_bins=31, interpolation="nearest", fill=0):
+        super().__init__(num_magnitude_bins, interpolation, fill)
+        self.num_ops, self.magnitude = int(num_ops), int(magnitude)
+        if self.num_ops < 0 or not 0 <= self.magnitude < self.num_magnitude_bins:
+            raise ValueError(f"RandAugment: num_ops must be >= 0 and magnitude in 0..{self.num_magnitude_bins - 1}, "
+                             f"got {num_ops}, {magnitude}")
+
+    def space(self, w, h):
+        return self._space(w, h, 0.3, 150.0 / 331.0 * w, 150.0 / 331.0 * h, 30.0, 0.9, 4)
+
+    def _index(self, table, generator):
+        return self.magnitude
+
+
+class TrivialAugmentWide(_PolicySampler):
+    """torchvision's TrivialAugmentWide on PIL images as a sampler of per-image policy programs: one op per image,
+    uniform over the fourteen POLICY_OPS, its magnitude a uniformly drawn table entry: shears to 0.99, translations
+    to 32 pixels, rotations to 135 degrees, enhancement factors 1 +- up to 0.99, posterize 8 down to 2 bits, solarize
+    thresholds 255 down to 0.  Draw order and tables: see _PolicySampler."""
+    num_ops = 1
+
+    def __init__(self, num_magnitude_bins=31, interpolation="nearest", fill=0):
+        super().__init__(num_magnitude_bins, interpolation, fill)
+
+    def space(self, w, h):
+        return self._space(w, h, 0.99, 32.0, 32.0, 135.0, 0.99, 6)
+
+    def _index(self, table, generator):
+        return int(torch.randint(len(table), (1,), dtype=torch.long, generator=generator))
+
+
 class TrainAugment:
     """ImageBatch -> ImageBatch with a random-resized-crop box and a flip bit per image, ``mode="square"``, and,
     with ``color`` (a ColorJitter), a colour record per image, and, with ``affine`` (a RandomAffine or a
-    RandomRotation) and the output size ``image_size``, an affine record per image.  Its own generator (``seed``)
-    makes a run reproducible; the colour records are drawn after the boxes and the flips and the affine records
-    last, so a seed gives the same boxes, flips and colour records with or without them."""
+    RandomRotation) and the output size ``image_size``, an affine record per image, and, with ``policy`` (a
+    RandAugment or a TrivialAugmentWide) and ``image_size``, a policy program per image.  Its own generator
+    (``seed``) makes a run reproducible; the colour records are drawn after the boxes and the flips, the affine
+    records after them and the policy programs last, so a seed gives the same boxes, flips, colour and affine records
+    with or without them."""
 
     def __init__(self, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, seed=0, color=None, affine=None,
-                 image_size=None):
+                 image_size=None, policy=None):
         self.scale, self.ratio, self.flip_p = tuple(scale), tuple(ratio), float(flip_p)
         self.generator = torch.Generator(device="cpu").manual_seed(int(seed))
         if color is not None and not isinstance(color, ColorJitter):
@@ -610,6 +924,9 @@ class TrainAugment:
         if affine is not None and not isinstance(affine, RandomAffine):
             raise ValueError("TrainAugment: affine must be a RandomAffine, a RandomRotation or None")
         self.affine = affine
+        if policy is not None and not isinstance(policy, _PolicySampler):
+            raise ValueError("TrainAugment: policy must be a RandAugment, a TrivialAugmentWide or None")
+        self.policy = policy
         self.image_size = None if image_size is None else int(image_size)
 
     def __call__(self, batch, image_size=None):
@@ -624,6 +941,13 @@ class TrainAugment:
                 raise ValueError("TrainAugment: affine records need the output size (image_size here or in the call): "
                                  "the matrices turn about the output's centre and translate by fractions of it")
             out = out.with_affine(self.affine.sample(len(batch), size, self.generator))
+        if self.policy is not None:
+            size = self.image_size if image_size is None else int(image_size)
+            if size is None:
+                raise ValueError("TrainAugment: policy programs need the output size (image_size here or in the call): "
+                                 "the translations are fractions of it and the rotations turn about its centre")
+            out = out.with_policy(self.policy.sample(len(batch), size, self.generator), self.policy.interpolation,
+                                  self.policy.fill)
         return out
 
 
