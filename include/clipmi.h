@@ -42,7 +42,9 @@ enum clipmi_dtype { CLIPMI_F32 = 0, CLIPMI_BF16 = 1, CLIPMI_FP8 = 2 /* MXFP8: OC
  * 10: clipmi_gemm_plan
  * 11: clipmi_sigmoid_pairs, clipmi_sigmoid_reduce (pairwise sigmoid contrastive head)
  * 12: clipmi_affine_u8 (affine / rotation augmentation of the input step)
- * 13: clipmi_enhance_u8 (posterize, solarize, autocontrast, equalize, sharpness: the policy ops of the input step) */
+ * 13: clipmi_enhance_u8 (posterize, solarize, autocontrast, equalize, sharpness: the policy ops of the input step)
+ * 14: clipmi_class_bce, clipmi_class_bias_grad (multi-label sigmoid / BCE head), clipmi_ap_count,
+ *     clipmi_multilabel_accumulate (average precision counts and thresholded multi-label tallies) */
 int clipmi_version(void);
 const char* clipmi_last_error(void);
 /* sha256 (hex) of the sources this library was compiled from (vlm-clip_amd/Makefile DIGEST_SRC) */
@@ -715,6 +717,22 @@ int clipmi_row_mean(void* stream, const float* v, int B, float* out);
  * dimg = scale d P, dprotos = scale d^T img.  gscale may be NULL (1). */
 int clipmi_class_ce_bwd(void* stream, const float* dscore, const float* img, const float* protos, int B, int C, int E,
                         float scale, const float* gscale, float* dimg, float* dprotos);
+/* Multi-label class scores (csrc/multilabel.hip; clipmi_version() >= 14): the scores of clipmi_class_scores, the
+ * same device function and so the same bits, plus bias[c] when bias is given ([C] or NULL), with a sigmoid / binary
+ * cross-entropy tail (torch.nn.BCEWithLogitsLoss) in place of the softmax / cross-entropy one: probs = sigmoid(z).
+ * With targets (fp32 [B, C] in [0, 1], soft labels allowed) and pw = pos_weight[c] ([C] or NULL = 1):
+ *   l[b, c]      = (1 - y) z + (1 + (pw - 1) y) (log1p(exp(-|z|)) + max(-z, 0))
+ *   loss_rows[b] = (1 / C) sum_c l[b, c]     (clipmi_row_mean of it = BCEWithLogitsLoss(pos_weight, "mean"))
+ *   dscore[b, c] = ((1 - y) sigmoid(z) - pw y (1 - sigmoid(z))) / C
+ * so clipmi_class_ce_bwd (which divides by B) turns dscore into dimg and dprotos unchanged.  A target outside
+ * [0, 1] or NaN sets *bad = 1 and contributes neither loss nor gradient.  Any output may be NULL; targets need bad,
+ * pos_weight needs targets.  B >= 1, E <= 1024, C <= 1024.  z = +-100 gives probs 1 / 0 and a finite loss. */
+int clipmi_class_bce(void* stream, const float* img, int B, int E, const float* desc, const int* off, int C,
+                     float scale, const float* bias, const float* targets, const float* pos_weight, float* scores,
+                     float* probs, float* loss_rows, float* dscore, int* bad);
+/* The bias gradient of the mean loss: dbias[c] = (gscale ? gscale[0] : 1) / B * sum_b dscore[b, c].  Fixed summation
+ * order (no float atomics): two runs give the same bits.  (clipmi_colsum has no scale and needs a workspace.) */
+int clipmi_class_bias_grad(void* stream, const float* dscore, int B, int C, const float* gscale, float* dbias);
 
 /* Row softmax of scale*x (fp32, y may alias x) and its backward dx = scale*y*(dy - <dy, y>):
  * the shared cross-attention adapter's probabilities (adapter/clip_adapter.py:117). */
@@ -793,6 +811,23 @@ int clipmi_topk_hits(void* stream, const int* top_idx, int N, int k, int M, cons
  * [0, C) sets *bad = 1 and is not counted.  probs [B, C] fp32 contiguous, labels int64 [B]. */
 int clipmi_classify_accumulate(void* stream, const float* probs, const int64_t* labels, int B, int C, int* pred,
                                float* conf, int64_t* confusion, int* bad);
+/* Multi-label metrics (csrc/eval_multilabel.hip; clipmi_version() >= 14).
+ * clipmi_ap_count: the integer counts behind average precision.  All four arrays are CLASS-MAJOR with one leading
+ * dimension ld >= N: element (sample i, class c) is at [c * ld + i] (scores fp32, targets uint8 0 / 1, ge_all and
+ * ge_pos int32).  For every class c and every positive i (target 1), with s the class's scores:
+ *   ge_all[i] = #{j : s[j] >= s[i]},   ge_pos[i] = #{j : target[j] == 1 and s[j] >= s[i]}     (both count i itself)
+ * entries of non-positives are written as 0, elements i >= N of a row are not touched, n_pos[c] (int32 [C]) = the
+ * number of positives.  Then AP_c = (1 / n_pos[c]) sum_{i positive} ge_pos[i] / ge_all[i] is exactly
+ * sklearn.metrics.average_precision_score, ties included.  A NaN score or a target other than 0 / 1 sets *bad = 1
+ * (+-inf scores are legal).  N * n_pos compares per class; integer results, independent of the launch geometry.
+ * clipmi_multilabel_accumulate: pred = probs >= thr[c] (thr fp32 [C], or NULL = 0.5), probs fp32 [B, C] and
+ * targets uint8 [B, C] row-major contiguous; counts[c * 4 + {0, 1, 2, 3}] += (tp, fp, fn, tn) (int64 [C, 4]) and
+ * exact_rows[0] += the rows whose whole prediction vector equals the target vector (integer atomics, summed per
+ * workgroup first).  A target other than 0 / 1 or a NaN probability sets *bad = 1.  C <= 1024. */
+int clipmi_ap_count(void* stream, const float* scores, const uint8_t* targets, int N, int C, int64_t ld, int* ge_all,
+                    int* ge_pos, int* n_pos, int* bad);
+int clipmi_multilabel_accumulate(void* stream, const float* probs, const uint8_t* targets, int B, int C,
+                                 const float* thr, int64_t* counts, int64_t* exact_rows, int* bad);
 
 /* ---- Live kernel timing (bench.py roofline) --------------------------------------------------
  * While armed, every launch whose variant label is in the comma-separated list `variants`

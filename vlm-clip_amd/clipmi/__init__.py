@@ -26,6 +26,9 @@ def __getattr__(name):
     if name in _EVALUATION:  # on-device retrieval ranks and classification metrics
         from . import evaluation
         return getattr(evaluation, name)
+    if name in _HEADS:  # the multi-label (sigmoid / BCE) feature-level head
+        from . import heads
+        return getattr(heads, name)
     raise AttributeError(name)
 
 
@@ -36,4 +39,6 @@ _IMAGES = ("ImageBatch", "preprocess", "random_resized_crop_boxes", "random_flip
 _EVALUATION = ("RankResult", "target_ranks", "TopK", "topk", "recall_at_k", "rank_summary", "evaluate_retrieval",
                "ClassificationMeter", "ClassificationResult", "classification_report", "accuracy", "evaluate_model",
                "evaluate_enhanced_model", "GroupRankResult", "group_ranks", "topk_relevance", "precision_at_k",
-               "average_precision_at_k")
+               "average_precision_at_k", "average_precision", "MultiLabelMeter", "MultiLabelResult",
+               "evaluate_multilabel")
+_HEADS = ("class_bce", "MultiLabelCLIPAdapter", "pos_weight_from_counts")

@@ -1,6 +1,6 @@
 """On-device evaluation: retrieval ranks for the contrastive model, classification metrics for the heads.
 
-Two families, both device-resident until one final transfer:
+Three families, all device-resident until one final transfer:
 
 * **Retrieval** (``target_ranks``, ``recall_at_k``, ``rank_summary``, ``evaluate_retrieval``): recall@K and
   median / mean rank of ``CLIPWithAdapters`` over a whole validation set.  The reference has no such metric
@@ -17,6 +17,10 @@ Two families, both device-resident until one final transfer:
   without sklearn: argmax, confidence and the confusion matrix accumulate on the device
   (``clipmi_classify_accumulate``), the report is formatted on the host from the confusion matrix in sklearn's
   layout.
+* **Multi-label classification** (``average_precision``, ``MultiLabelMeter``, ``evaluate_multilabel``): EMOTIC's
+  metric, mean average precision over the categories, exactly sklearn's ``average_precision_score`` from integer
+  counts taken on the device (csrc/eval_multilabel.hip), and the thresholded per-class tp / fp / fn / tn with the
+  scores derived from them, for ``heads.MultiLabelCLIPAdapter``.
 
 One documented difference from the reference, shared by both ``evaluate_*`` functions: the confusion matrix
 always covers all C classes (utils.py:61 does the same with ``labels=range(C)``; evaluation.py:54 lets sklearn
@@ -48,6 +52,8 @@ _lib.declare("clipmi_group_pick", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int
 _lib.declare("clipmi_group_count", [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp])
 _lib.declare("clipmi_topk_hits", [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_ap_count", [c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_multilabel_accumulate", [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp])
 
 P_, call = T.P_, T.call
 
@@ -794,3 +800,222 @@ def evaluate_enhanced_model(model, test_loader, emotions=EMOTIONS):
         return 0.0, np.zeros((C, C)), "No data to report.", [], [], paths, [], np.array([]), contexts
     acc, cm, report, preds, labs, confs, probs = _finish(meter, list(emotions))
     return acc, cm, report, preds, labs, paths, confs, probs, contexts
+
+
+# ------------------------------------------------------------------------------ multi-label classification
+def _binary_u8(targets):
+    """Targets as the kernels read them: uint8 with 1 / 0 where the value is exactly 1 / 0 and 2 (which sets
+    ``bad``) anywhere else, so a soft label or a NaN is reported instead of truncated."""
+    t = targets.detach()
+    two = torch.full((), 2, dtype=torch.uint8, device=t.device)
+    return torch.where(t == 1, torch.ones_like(two), torch.where(t == 0, torch.zeros_like(two), two))
+
+
+def _ap_counts(scores_cm, targets_cm):
+    """clipmi_ap_count on class-major device tensors (fp32 / uint8 [C, N], contiguous): -> (ge_all, ge_pos int32
+    [C, N], n_pos int32 [C], bad int32 [1]), all on the device; no host synchronisation."""
+    C, N = scores_cm.shape
+    dev = scores_cm.device
+    ge_all = torch.empty(C, N, dtype=torch.int32, device=dev)
+    ge_pos = torch.empty_like(ge_all)
+    n_pos = torch.empty(C, dtype=torch.int32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("clipmi_ap_count", T.K.stream(), P_(scores_cm), P_(targets_cm), N, C, N, P_(ge_all), P_(ge_pos), P_(n_pos),
+         P_(bad))
+    return ge_all, ge_pos, n_pos, bad
+
+
+def ap_from_counts(ge_all, ge_pos, n_pos):
+    """AP per class from clipmi_ap_count's integers (host, class-major [C, N]): (1 / n_pos) * the sum over the
+    positives, in index order and in float64, of ge_pos / ge_all; nan where a class has no positive."""
+    ge_all = np.asarray(ge_all, np.int64)
+    ge_pos = np.asarray(ge_pos, np.float64)
+    n_pos = np.asarray(n_pos, np.int64)
+    C = n_pos.shape[0]
+    ratio = np.divide(ge_pos, ge_all, out=np.zeros(ge_pos.shape, np.float64), where=ge_all > 0)
+    total = np.cumsum(ratio, axis=1)[:, -1] if ratio.shape[1] else np.zeros(C)  # cumsum: strictly in index order
+    return np.divide(total, n_pos, out=np.full(C, np.nan), where=n_pos > 0)
+
+
+def _nanmean(x):
+    x = np.asarray(x, np.float64)
+    keep = ~np.isnan(x)
+    return float(x[keep].mean()) if keep.any() else float("nan")
+
+
+def _to_host(parts, dtypes):
+    """One device-to-host transfer of several tensors -> numpy copies, flat."""
+    blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+    out, off = [], 0
+    for t, dtype in zip(parts, dtypes):
+        out.append(np.frombuffer(blob, dtype=dtype, count=t.numel(), offset=off).copy())
+        off += t.numel() * t.element_size()
+    return out
+
+
+def _multilabel_operands(who, scores, targets):
+    if scores.dim() != 2 or tuple(targets.shape) != tuple(scores.shape):
+        raise ValueError(f"{who}: scores and targets must both be [N, C], got {tuple(scores.shape)} and "
+                         f"{tuple(targets.shape)}")
+    if not scores.is_cuda:
+        raise ValueError(f"{who} needs GPU tensors (no CPU fallback)")
+    if scores.shape[0] <= 0 or scores.shape[1] <= 0:
+        raise ValueError(f"{who}: empty input")
+
+
+def average_precision(scores, targets):
+    """-> (ap float64 [C], n_pos int64 [C]) (numpy): per class ``sklearn.metrics.average_precision_score(targets[:,
+    c], scores[:, c])`` of device tensors scores [N, C] (any float dtype, read as fp32; +-inf allowed) and targets
+    [N, C] (0 / 1 in any dtype), ties included: one threshold per distinct score.  mAP = ``np.nanmean(ap)``.
+
+    The O(N^2 C) comparisons run in clipmi_ap_count and yield integers (for each positive, how many samples and how
+    many positives score at least as high), so the result does not depend on any summation order on the device;
+    the host adds ``ge_pos / ge_all`` in float64 in index order.  One transfer.  Difference from sklearn: a class
+    without positives gets ``nan`` and drops out of the mean, where sklearn returns 0.0 with a warning (its
+    newer versions) and so pulls the mean down by a class that measures nothing.  A NaN score or a target other
+    than 0 / 1 raises ValueError."""
+    targets = torch.as_tensor(targets)
+    _multilabel_operands("average_precision", scores, targets)
+    dev = scores.device
+    s = scores.detach().to(torch.float32).t().contiguous()
+    t8 = _binary_u8(targets.to(dev)).t().contiguous()
+    ge_all, ge_pos, n_pos, bad = _ap_counts(s, t8)
+    C, N = s.shape
+    ga, gp, npos, b = _to_host([ge_all, ge_pos, n_pos, bad], (np.int32,) * 4)
+    if int(b[0]):
+        raise ValueError("average_precision: a score is NaN or a target is not 0 / 1")
+    return ap_from_counts(ga.reshape(C, N), gp.reshape(C, N), npos), npos.astype(np.int64)
+
+
+@dataclass
+class MultiLabelResult:
+    """Host copies (numpy) of a ``MultiLabelMeter``.  counts int64 [C, 4] = (tp, fp, fn, tn) per class at the
+    meter's thresholds; ap float64 [C] (nan for a class without positives) and mAP = nanmean(ap), threshold-free;
+    precision / recall / f1 float64 [C] and support int64 [C] (= tp + fn), micro_f1, macro_f1, subset_accuracy
+    (rows predicted exactly) and hamming_loss (wrong cells / all cells), all from the integer counts with
+    zero_division=0; probs float32 [n, C], targets uint8 [n, C]."""
+    n: int
+    counts: np.ndarray
+    exact_rows: int
+    ap: np.ndarray
+    mAP: float
+    precision: np.ndarray
+    recall: np.ndarray
+    f1: np.ndarray
+    support: np.ndarray
+    micro_f1: float
+    macro_f1: float
+    subset_accuracy: float
+    hamming_loss: float
+    probs: Optional[np.ndarray] = None
+    targets: Optional[np.ndarray] = None
+
+    @classmethod
+    def from_counts(cls, counts, exact_rows, n, ap, probs=None, targets=None):
+        """The derived numbers from the integers: what sklearn's precision_recall_fscore_support (per class,
+        average="micro" / "macro", zero_division=0), accuracy_score and hamming_loss give on the same
+        thresholded predictions."""
+        counts = np.asarray(counts, np.int64).reshape(-1, 4)
+        C, n = counts.shape[0], int(n)
+        tp, fp, fn = counts[:, 0], counts[:, 1], counts[:, 2]
+        f1 = _div(2 * tp, 2 * tp + fp + fn)
+        ap = np.asarray(ap, np.float64)
+        return cls(n=n, counts=counts, exact_rows=int(exact_rows), ap=ap, mAP=_nanmean(ap),
+                   precision=_div(tp, tp + fp), recall=_div(tp, tp + fn), f1=f1, support=tp + fn,
+                   micro_f1=float(_div(2 * tp.sum(), 2 * tp.sum() + fp.sum() + fn.sum())),
+                   macro_f1=float(f1.mean()) if C else 0.0,
+                   subset_accuracy=float(_div(int(exact_rows), n)),
+                   hamming_loss=float(_div(fp.sum() + fn.sum(), n * C)), probs=probs, targets=targets)
+
+
+class MultiLabelMeter:
+    """Device-resident tallies of a multi-label run, the sibling of ``ClassificationMeter``: per batch
+    ``update(probs, targets)`` keeps the rows and adds pred = probs >= threshold into per-class (tp, fp, fn, tn)
+    and the exact-row count (clipmi_multilabel_accumulate) without a host synchronisation; ``result()`` runs
+    clipmi_ap_count over the kept rows and makes one transfer.  threshold: a float, or one per class."""
+
+    def __init__(self, num_classes, capacity=0, threshold=0.5):
+        if int(num_classes) <= 0:
+            raise ValueError("MultiLabelMeter: num_classes must be positive")
+        self.C = int(num_classes)
+        self._capacity = int(capacity)
+        thr = np.asarray(threshold, np.float32)
+        if thr.shape not in ((), (self.C,)) or np.isnan(thr).any():
+            raise ValueError(f"MultiLabelMeter: threshold must be a number or {self.C} numbers")
+        self.threshold = np.broadcast_to(thr, (self.C,)).copy()
+        self.counts = None
+
+    def _alloc(self, device):
+        C, cap = self.C, self._capacity
+        self.counts = torch.zeros(C, 4, dtype=torch.int64, device=device)
+        self.exact = torch.zeros(1, dtype=torch.int64, device=device)
+        self.bad = torch.zeros(1, dtype=torch.int32, device=device)
+        self.thr = torch.from_numpy(self.threshold).to(device)
+        self.probs = _Rows((C,), torch.float32, device, cap)
+        self.targets = _Rows((C,), torch.uint8, device, cap)
+
+    @property
+    def n(self):
+        return 0 if self.counts is None else self.probs.n
+
+    def update(self, probs, targets):
+        if probs.dim() != 2 or probs.shape[1] != self.C:
+            raise ValueError(f"MultiLabelMeter: probs must be [B, {self.C}], got {tuple(probs.shape)}")
+        if not probs.is_cuda:
+            raise ValueError("MultiLabelMeter needs GPU probabilities (no CPU fallback)")
+        B = probs.shape[0]
+        targets = torch.as_tensor(targets)
+        if tuple(targets.shape) != (B, self.C):
+            raise ValueError(f"MultiLabelMeter: targets must have shape ({B}, {self.C}), got {tuple(targets.shape)}")
+        if B == 0:
+            return
+        if self.counts is None:
+            self._alloc(probs.device)
+        p, t = self.probs.take(B), self.targets.take(B)
+        p.copy_(probs.detach())
+        t.copy_(_binary_u8(targets.to(probs.device, non_blocking=True)))
+        call("clipmi_multilabel_accumulate", T.K.stream(), P_(p), P_(t), B, self.C, P_(self.thr), P_(self.counts),
+             P_(self.exact), P_(self.bad))
+
+    def result(self) -> MultiLabelResult:
+        """One device-to-host transfer of everything; ValueError if a target was not 0 / 1 or a probability NaN."""
+        C = self.C
+        if self.counts is None:
+            return MultiLabelResult.from_counts(np.zeros((C, 4), np.int64), 0, 0, np.full(C, np.nan),
+                                                np.zeros((0, C), np.float32), np.zeros((0, C), np.uint8))
+        n = self.probs.n
+        ge_all, ge_pos, n_pos, ap_bad = _ap_counts(self.probs.rows().t().contiguous(),
+                                                   self.targets.rows().t().contiguous())
+        parts = [self.counts, self.exact, self.bad, ap_bad, n_pos, ge_all, ge_pos, self.probs.rows(),
+                 self.targets.rows()]
+        counts, exact, bad, ap_bad, n_pos, ge_all, ge_pos, probs, targets = _to_host(
+            parts, (np.int64, np.int64, np.int32, np.int32, np.int32, np.int32, np.int32, np.float32, np.uint8))
+        if int(bad[0]) or int(ap_bad[0]):
+            raise ValueError("MultiLabelMeter: a target is not 0 / 1 or a probability is NaN")
+        ap = ap_from_counts(ge_all.reshape(C, n), ge_pos.reshape(C, n), n_pos)
+        return MultiLabelResult.from_counts(counts, exact[0], n, ap, probs.reshape(n, C), targets.reshape(n, C))
+
+
+def evaluate_multilabel(model, loader, threshold=0.5, use_all_descriptions=False) -> MultiLabelResult:
+    """``heads.MultiLabelCLIPAdapter`` over the reference's EMOTIC batches ``(context image, body crop, categorical
+    [B, C], continuous)``: sigmoid probabilities from ``predict`` (or ``predict_with_all_descriptions``) into a
+    ``MultiLabelMeter``; the body crop is passed on when the model was built with body=True, the continuous values
+    are ignored.  Replaces the host loop of ``sklearn.metrics.average_precision_score`` per category."""
+    _eval_mode(getattr(model, "model", None), getattr(model, "visual_adapter", None),
+               getattr(model, "text_adapter", None), getattr(model, "body_adapter", None))
+    meter = None
+    with torch.no_grad():
+        for context, body, categorical, _continuous in loader:
+            dev = _cuda()
+            context = context.to(dev, non_blocking=True)
+            args = (context, body.to(dev, non_blocking=True)) if getattr(model, "body", False) else (context,)
+            if use_all_descriptions and hasattr(model, "predict_with_all_descriptions"):
+                probs = model.predict_with_all_descriptions(*args)
+            else:
+                probs = model.predict(*args)
+            if meter is None:
+                meter = MultiLabelMeter(probs.shape[1], _dataset_len(loader), threshold)
+            meter.update(probs, categorical)
+    if meter is None:
+        raise ValueError("evaluate_multilabel: the loader is empty")
+    return meter.result()

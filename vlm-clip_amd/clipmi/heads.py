@@ -39,6 +39,9 @@ _lib.declare("clipmi_class_scores", [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int
                                      c_vp, c_vp])
 _lib.declare("clipmi_row_mean", [c_vp, c_vp, c_int, c_vp])
 _lib.declare("clipmi_class_ce_bwd", [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_float, c_vp, c_vp, c_vp])
+_lib.declare("clipmi_class_bce", [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp])
+_lib.declare("clipmi_class_bias_grad", [c_vp, c_vp, c_int, c_int, c_vp, c_vp])
 
 P_, call = T.P_, T.call
 
@@ -183,6 +186,57 @@ def class_scores(img, desc, offsets, scale, labels=None):
     call("clipmi_class_scores", T.K.stream(), P_(img.contiguous()), B, E, P_(desc.contiguous()), P_(offsets), C,
          float(scale), P_(scores), P_(probs), P_(labels), P_(loss_rows), P_(dscore), P_(bad))
     return scores, probs, loss_rows, dscore, bad
+
+
+def _class_vector(who, name, v, C, dev):
+    """An optional per-class fp32 vector ([C]) on the features' device."""
+    if v is None:
+        return None
+    v = torch.as_tensor(v).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if v.shape != (C,):
+        raise ValueError(f"{who}: {name} must have shape ({C},), got {tuple(v.shape)}")
+    return v
+
+
+def class_bce(img, desc, offsets, scale, targets=None, pos_weight=None, bias=None):
+    """-> (scores [B, C], probs [B, C], loss_rows, dscore, bad): ``class_scores`` with a sigmoid / binary
+    cross-entropy tail (clipmi_class_bce).  scores = the max over each class's descriptions (+ bias [C]), bit
+    for bit ``class_scores``' when bias is None; probs = sigmoid(scores).  With targets (float [B, C] in [0, 1],
+    soft labels allowed) and pos_weight ([C] or None): loss_rows[b] = the mean over the classes of torch's
+    ``BCEWithLogitsLoss`` terms, so ``loss_rows.mean()`` is its ``reduction="mean"``, and dscore = d loss_rows /
+    d scores, which ``clipmi_class_ce_bwd`` takes as it takes the cross-entropy's.  bad (int32 [1]) is set by a
+    target outside [0, 1] or NaN.  The last three are None without targets."""
+    B, E = img.shape
+    C = offsets.numel() - 1
+    dev = img.device
+    scores = torch.empty(B, C, dtype=torch.float32, device=dev)
+    probs = torch.empty_like(scores)
+    loss_rows = dscore = bad = None
+    bias = _class_vector("class_bce", "bias", bias, C, dev)
+    if targets is not None:
+        targets = torch.as_tensor(targets).detach().to(device=dev, dtype=torch.float32).contiguous()
+        if targets.shape != (B, C):
+            raise ValueError(f"class_bce: targets must have shape ({B}, {C}), got {tuple(targets.shape)}")
+        pos_weight = _class_vector("class_bce", "pos_weight", pos_weight, C, dev)
+        loss_rows = torch.empty(B, dtype=torch.float32, device=dev)
+        dscore = torch.empty_like(scores)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif pos_weight is not None:
+        raise ValueError("class_bce: pos_weight needs targets")
+    call("clipmi_class_bce", T.K.stream(), P_(img.contiguous()), B, E, P_(desc.contiguous()), P_(offsets), C,
+         float(scale), P_(bias), P_(targets), P_(pos_weight), P_(scores), P_(probs), P_(loss_rows), P_(dscore),
+         P_(bad))
+    return scores, probs, loss_rows, dscore, bad
+
+
+def pos_weight_from_counts(n_pos, n):
+    """``BCEWithLogitsLoss``'s pos_weight from the label counts of a training set: (n - n_pos) / n_pos per class,
+    negatives over positives; a class without positives gets 1.  -> float32 [C] (CPU)."""
+    n_pos = torch.as_tensor(n_pos).detach().to("cpu", torch.float64).reshape(-1)
+    n = float(n)
+    if n <= 0 or bool(((n_pos < 0) | (n_pos > n)).any()):
+        raise ValueError("pos_weight_from_counts: counts must satisfy 0 <= n_pos <= n, n > 0")
+    return torch.where(n_pos > 0, (n - n_pos) / n_pos.clamp(min=1.0), torch.ones_like(n_pos)).to(torch.float32)
 
 
 class _Backbone:
@@ -363,6 +417,188 @@ class ZeroShotEmotionRecognition:
 
 class ContextAdapter(FeatureAdapter):
     """model_v.ContextAdapter (:30-31): the BaseAdapter bottleneck on VLM context features."""
+
+
+class MultiLabelCLIPAdapter:
+    """The CLIP-Adapter head for multi-label data (EMOTIC: 26 categories, several per person): ``CLIPAdapter``'s
+    backbone, description bank and visual / text ``FeatureAdapter``s, with independent sigmoids in place of the
+    softmax: logits = T * img . protos^T + class_bias, loss = ``BCEWithLogitsLoss(pos_weight)`` (mean over
+    B * C), all in csrc/multilabel.hip (clipmi_class_bce, clipmi_class_bias_grad) and the existing head kernels
+    (clipmi_class_ce_bwd, the adapters' backward, clipmi_adamw with weight decay 0 == torch.optim.Adam).
+
+    ``model_name`` is as for ``CLIPAdapter`` (a name / local path, or an object with ``get_text_features``,
+    ``get_image_features``, ``logit_scale``); descriptions are ``{category: (input_ids, attention_mask)}``.
+    pos_weight: [C] or None (``pos_weight_from_counts``).  class_bias: a trained per-class logit offset [C],
+    initialised to bias_init, with its own flat Adam state (the prior of a rare category: a cosine logit alone
+    cannot express "rarely present").  body=True adds ``body_adapter``: the body crop's image features go through
+    it and are fused with the context image's by clipmi_fuse_avg, as ``EnhancedCLIPAdapter`` fuses image and
+    context; with body=False the body tensors of a batch are ignored.
+
+    T = exp(logit_scale) in training and in ``predict`` / ``predict_with_all_descriptions`` alike (``CLIPAdapter``
+    predicts at 100 whatever it trained at; a trained bias only means the same thing at the same temperature)."""
+
+    def __init__(self, model_name, alpha=0.2, beta=0.2, bottleneck_dim=64, descriptions=None, pos_weight=None,
+                 class_bias=True, bias_init=0.0, body=False, device="cuda", precision="fp32", seed=0):
+        self.model = _Backbone(model_name, device, precision) if isinstance(model_name, str) else model_name
+        self.processor = None
+        dim = int(self.model.m.config.projection_dim if isinstance(self.model, _Backbone)
+                  else self.model.projection_dim)
+        self.image_feature_dim = self.text_feature_dim = dim
+        self.visual_adapter = VisualAdapter(dim, bottleneck_dim, device, seed=seed)
+        self.text_adapter = TextAdapter(dim, bottleneck_dim, device, seed=seed + 1)
+        self.body_adapter = VisualAdapter(dim, bottleneck_dim, device, seed=seed + 2) if body else None
+        self.alpha, self.beta, self.body = alpha, beta, bool(body)
+        if descriptions is None:
+            raise ValueError("descriptions {category: (input_ids, attention_mask)} are required (no tokenizer offline)")
+        self.emotion_descriptions = descriptions
+        self.encode_emotion_descriptions()
+        C, dev = self.emotion_embedding_tensor.shape[0], self.emotion_embedding_tensor.device
+        self.pos_weight = _class_vector("MultiLabelCLIPAdapter", "pos_weight", pos_weight, C, dev)
+        self.class_bias = None
+        if class_bias:
+            self.class_bias = torch.full((C,), float(bias_init), dtype=torch.float32, device=dev)
+            self.bias_grad = torch.zeros_like(self.class_bias)
+            self.bias_exp_avg = torch.zeros_like(self.class_bias)
+            self.bias_exp_avg_sq = torch.zeros_like(self.class_bias)
+            self.bias_step_count = 0
+
+    def encode_emotion_descriptions(self):
+        self._bank = _DescriptionBank()
+        self._bank.encode(self.model, self.emotion_descriptions)
+        self.emotion_embedding_tensor = self._bank.protos
+        self.adapted_emotion_embedding_tensor = None
+
+    def update_emotion_embeddings(self):
+        self.adapted_emotion_embedding_tensor, _ = self.text_adapter.blend(self.emotion_embedding_tensor, self.beta,
+                                                                           False)
+
+    def _adapters(self):
+        return [a for a in (self.visual_adapter, self.text_adapter, self.body_adapter) if a is not None]
+
+    def temperature(self):
+        return float(self.model.logit_scale.detach().float().exp().item())
+
+    def _image(self, pixel_values, body_pixel_values):
+        """-> (features [B, E], (s_img, s_body, s_fuse) for backward): the context image through the visual
+        adapter, with body=True fused with the body crop through the body adapter."""
+        img, s_img = self.visual_adapter.blend(self.model.get_image_features(pixel_values), self.alpha, True)
+        if not self.body:
+            return img, (s_img, None, None)
+        if body_pixel_values is None:
+            raise ValueError("MultiLabelCLIPAdapter(body=True) needs body_pixel_values")
+        bod, s_body = self.body_adapter.blend(self.model.get_image_features(body_pixel_values), self.alpha, True)
+        if bod.shape != img.shape:
+            raise ValueError(f"context and body batches differ: {tuple(img.shape)} and {tuple(bod.shape)}")
+        fused = torch.empty_like(img)
+        ru = torch.empty(img.shape[0], dtype=torch.float32, device=img.device)
+        call("clipmi_fuse_avg", T.K.stream(), P_(img), P_(bod), img.shape[0], img.shape[1], P_(fused), P_(ru))
+        return fused, (s_img, s_body, (fused, ru))
+
+    def _host_targets(self, targets):
+        """Targets checked on the host before anything is updated (torch's BCE raises before optimizer.step() on
+        a target outside [0, 1]): -> float32 [B, C] on the CPU."""
+        C = self.emotion_embedding_tensor.shape[0]
+        y = torch.as_tensor(targets).detach().to("cpu", torch.float32)
+        if y.dim() != 2 or y.shape[1] != C:
+            raise ValueError(f"targets must be [B, {C}], got {tuple(y.shape)}")
+        if not bool(((y >= 0) & (y <= 1)).all()):
+            raise ValueError("all elements of target should be between 0 and 1")
+        return y
+
+    def train_step(self, pixel_values, targets, learning_rate, temperature, body_pixel_values=None):
+        """features -> adapters (-> fusion) -> clipmi_class_bce -> clipmi_class_ce_bwd -> Adam over the adapters
+        and the class bias; -> (loss [1], bad [1]) on the device."""
+        y = self._host_targets(targets)
+        img, (s_img, s_body, s_fuse) = self._image(pixel_values, body_pixel_values)
+        txt, s_txt = self.text_adapter.blend(self.emotion_embedding_tensor, self.beta, False)
+        _, _, loss_rows, dscore, bad = class_bce(img, txt, self._bank.protos_offsets, temperature, y, self.pos_weight,
+                                                 self.class_bias)
+        B, C, E = img.shape[0], txt.shape[0], img.shape[1]
+        loss = torch.empty(1, dtype=torch.float32, device=img.device)
+        call("clipmi_row_mean", T.K.stream(), P_(loss_rows), B, P_(loss))
+        dimg, dtxt = torch.empty_like(img), torch.empty_like(txt)
+        call("clipmi_class_ce_bwd", T.K.stream(), P_(dscore), P_(img), P_(txt), B, C, E, float(temperature), None,
+             P_(dimg), P_(dtxt))
+        for ad in self._adapters():
+            ad.grad.zero_()  # optimizer.zero_grad()
+        if s_fuse is not None:
+            dab = torch.empty_like(dimg)
+            call("clipmi_fuse_avg_bwd", T.K.stream(), P_(dimg), P_(s_fuse[0]), P_(s_fuse[1]), B, E, P_(dab))
+            self.visual_adapter.backward_(dab, s_img)
+            self.body_adapter.backward_(dab, s_body)
+        else:
+            self.visual_adapter.backward_(dimg, s_img)
+        self.text_adapter.backward_(dtxt, s_txt)
+        for ad in self._adapters():
+            ad.adam_step(learning_rate)
+        if self.class_bias is not None:
+            call("clipmi_class_bias_grad", T.K.stream(), P_(dscore), B, C, None, P_(self.bias_grad))
+            self.bias_step_count += 1
+            call("clipmi_adamw", T.K.stream(), P_(self.class_bias), P_(self.bias_grad), P_(self.bias_exp_avg),
+                 P_(self.bias_exp_avg_sq), None, C, float(learning_rate), 0.9, 0.999, 1e-8, 0.0,
+                 self.bias_step_count, None)
+        return loss, bad
+
+    def train(self, train_loader, num_epochs=50, learning_rate=3e-4):
+        """Adam over the adapters (and the bias) on the reference's EMOTIC batches ``(context image, body crop,
+        categorical [B, C] float one-hot, continuous [B, 3])``; the continuous valence / arousal / dominance values
+        are ignored (no regression head), and so is the body crop unless body=True.  The adapted category
+        embeddings are refreshed after every epoch, as ``CLIPAdapter.train`` does; -> the per-epoch mean losses."""
+        temperature = self.temperature()
+        history = []
+        for _ in range(num_epochs):
+            losses = []
+            for context, body, categorical, _continuous in train_loader:
+                loss, _ = self.train_step(context, categorical, learning_rate, temperature,
+                                          body if self.body else None)
+                losses.append(loss)
+            history.append(float(torch.cat(losses).mean().item()))
+            self.update_emotion_embeddings()
+        self.update_emotion_embeddings()
+        return history
+
+    def predict(self, pixel_values, body_pixel_values=None):
+        """Sigmoid probabilities [B, C] against the adapted category embeddings."""
+        img, _ = self._image(pixel_values, body_pixel_values)
+        protos = self.adapted_emotion_embedding_tensor
+        if protos is None:
+            protos = self.emotion_embedding_tensor
+        return class_bce(img, protos, self._bank.protos_offsets, self.temperature(), bias=self.class_bias)[1]
+
+    def predict_with_all_descriptions(self, pixel_values, body_pixel_values=None):
+        """Sigmoid probabilities [B, C]: every description through the text adapter, the max per category."""
+        img, _ = self._image(pixel_values, body_pixel_values)
+        desc, _ = self.text_adapter.blend(self._bank.desc, self.beta, False)
+        return class_bce(img, desc, self._bank.offsets, self.temperature(), bias=self.class_bias)[1]
+
+    def _ckpt_keys(self):
+        keys = [("visual_adapter_state_dict", self.visual_adapter), ("text_adapter_state_dict", self.text_adapter)]
+        if self.body:
+            keys.append(("body_adapter_state_dict", self.body_adapter))
+        return keys
+
+    def save_adapter_weights(self, path):
+        """``EnhancedCLIPAdapter``'s checkpoint layout ({name}_adapter_state_dict -> nn.Linear state dicts) plus
+        ``class_bias`` ([C]) when the head has one."""
+        sd = {k: ad.state_dict() for k, ad in self._ckpt_keys()}
+        if self.class_bias is not None:
+            sd["class_bias"] = self.class_bias.detach().cpu().clone()
+        torch.save(sd, path)
+
+    def load_adapter_weights(self, path):
+        """Reads ``save_adapter_weights``' file (safe loader) and refreshes the adapted category embeddings; a
+        missing file raises FileNotFoundError, a missing key KeyError."""
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"No adapter weights found at {path}")
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        for k, ad in self._ckpt_keys():
+            ad.load_state_dict(sd[k])
+        if self.class_bias is not None:
+            b = torch.as_tensor(sd["class_bias"], dtype=torch.float32)
+            if b.shape != self.class_bias.shape:
+                raise ValueError(f"class_bias: shape {tuple(b.shape)} != {tuple(self.class_bias.shape)}")
+            self.class_bias.copy_(b)
+        self.update_emotion_embeddings()
 
 
 class EnhancedCLIPAdapter(nn.Module):

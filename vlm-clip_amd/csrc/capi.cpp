@@ -23,6 +23,6 @@ int clipmi_invalid(const std::string& msg) {
 #define CLIPMI_SRC_DIGEST "unknown"
 #endif
 
-extern "C" int clipmi_version(void) { return 13; }
+extern "C" int clipmi_version(void) { return 14; }
 extern "C" const char* clipmi_build_digest(void) { return CLIPMI_SRC_DIGEST; }
 extern "C" const char* clipmi_last_error(void) { return g_last_error.c_str(); }

@@ -12,11 +12,13 @@
 // deterministic per-element reductions over the batch (no atomics).
 #include "common.h"
 #include "internal.h"
+#include "class_score.h"
 
 namespace {
 
 constexpr int HT = 256;  // threads per workgroup
 constexpr int MAXE = 1024, MAXA = 256, MAXC = 1024;
+static_assert(HT == CLASS_THREADS && MAXE == CLASS_MAXE && MAXC == CLASS_MAXC, "class_score.h's geometry");
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
   v = wave_sum(v);
@@ -149,18 +151,7 @@ __global__ __launch_bounds__(HT) void class_scores_kernel(const float* img, int 
   __shared__ float stat[2];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int64_t row = blockIdx.x;
-  for (int e = t; e < E; e += HT) simg[e] = img[row * E + e];
-  __syncthreads();
-  for (int c = w; c < C; c += HT / 64) {
-    float best = -__builtin_huge_valf();
-    for (int j = off[c]; j < off[c + 1]; ++j) {
-      float acc = 0.f;
-      for (int e = lane; e < E; e += 64) acc = fmaf(desc[(int64_t)j * E + e], simg[e], acc);
-      best = fmaxf(best, scale * wave_sum(acc));
-    }
-    if (lane == 0) sc[c] = best;
-  }
-  __syncthreads();
+  class_max_scores(img, row, E, desc, off, C, scale, simg, sc);  // class_score.h, shared with multilabel.hip
   if (w == 0) {
     float m = -__builtin_huge_valf();
     for (int c = lane; c < C; c += 64) m = fmaxf(m, sc[c]);
